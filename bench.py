@@ -12,16 +12,21 @@ Pipelining (the default, ``value``): step k issues network(k) on the main stream
 event, and issues ICC(k) + the pose all-gather on a second stream that WAITS on that event --
 ICC(k) is ordered after the network pass that produces its poses and overlaps network(k+1),
 the way a deployment refines frame k while the network runs on frame k+1.  Every step executes
-both stages completely.  ``--no-overlap`` runs them back to back on one stream; the JSON always
-carries the serial stage times (``stage_ms``, ``value_serial``), the rate of the hand-written
-volumetric path alone (``value_handwritten_path``: voxelize + 3-D CNN + heads + ICC, stock 2-D
-backbone excluded) and the batch-1 latency of BASELINE configs[1] (``latency_batch1_ms``).
+both stages completely.  ``--no-overlap`` runs them back to back on one stream.
+A plain run sets up, warms up, times ``--steps`` steps and prints the headline line (``value``,
+``ms_per_step``, ...).  ``--full`` adds everything else the bench measures, after the timed steps:
+the serial stage times (``stage_ms``, ``value_serial``), the rate of the hand-written volumetric
+path alone (``value_handwritten_path``: voxelize + 3-D CNN + heads + ICC, stock 2-D backbone
+excluded), the rooflines, the accuracy of the refined poses, the CPU baseline, the 8-scene and
+training extras and the batch-1 latency of BASELINE configs[1] (``latency_batch1_ms``).
+``--dump-outputs DIR`` writes the arrays the last timed step computed as ``DIR/<name>.npy``.
 Inputs are resident in HBM before the timed region.  Weights are random (no pretrained file is
 reachable offline), so the network's poses carry no information: the ICC stage consumes the
 network's pose tensor only as its ordering dependency and starts from the scene's synthetic
 perturbed-ground-truth poses -- same work, real grids.
 
-Contract: python bench.py --gpus N --steps K --warmup W  -> ONE JSON line on rank 0.
+Contract: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+          -> ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -48,6 +53,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline: stage breakdown, "
+                         "hand-written path, rooflines, accuracy, CPU baseline, 8-scene / training extras, "
+                         "batch-1 latency (the --no-* options below trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float32, <= 64 MB "
+                         "in all; inputs are seeded, so two builds can be compared output for output)")
     ap.add_argument("--scenes-per-gpu", type=int, default=1)
     ap.add_argument("--objects", type=int, default=8)
     ap.add_argument("--icc-iters", type=int, default=100)
@@ -183,6 +195,7 @@ class Workload:
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.args.dtype == "bf16"):
             rot, trans, conf = self.model.predict(**self.inputs)
         rot, trans, conf = rot.float(), trans.float(), conf.float()
+        self.last_predict = dict(network_rot=rot, network_trans=trans, network_conf=conf)  # for --dump-outputs
         idx = conf.argmax(dim=1)
         ar = torch.arange(self.B, device=self.device)
         return torch.cat([rot[ar, idx], trans[ar, idx]], dim=1)  # [B,7] network poses
@@ -245,6 +258,25 @@ def gather_evidence(wl, device):
     out, _ = wl.step()
     return dict(gathered_rows=int(out.shape[0]), rows_per_rank=int(wl.B),
                 ranks_seen=parallel.rank_census(device))
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(dirname, arrays):
+    """``--dump-outputs``: each array as ``dirname/<name>.npy`` in float32 (float64 stays float64).  An array larger
+    than its share of the 64 MB limit is replaced by a fixed, seeded sample of its elements (flattened, in index order),
+    the same sample for the same shape in every run."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            flat = a.reshape(-1)
+            keep = np.sort(np.random.RandomState(0).choice(flat.size, share // a.itemsize, replace=False))
+            a = flat[keep]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
 
 
 def time_kernel_live(fn, reps):
@@ -808,7 +840,14 @@ def dry_run_cpu(args, world, rank):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo", rank=rank, world_size=world)
     wl = StubWorkload(args, rank, device)
-    elapsed = parallel.timed_steps(wl.step, args.steps, args.warmup, device=None)
+    last = {}
+
+    def step():
+        last["poses"], _ = wl.step()
+
+    elapsed = parallel.timed_steps(step, args.steps, args.warmup, device=None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     ev = gather_evidence(wl, device)
     expect = torch.arange(world * wl.B, dtype=torch.float32) * 10.0
     ev["rank_order_ok"] = bool(torch.equal(wl.step()[0][:, 0].cpu(), expect))
@@ -825,6 +864,68 @@ def dry_run_cpu(args, world, rank):
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def full_extras(args, wl, world, rank, device, out, lap):
+    """``--full``: the un-timed measurements beside the headline, added to rank 0's line ``out``: stage breakdown,
+    live kernel timing, rooflines, accuracy, CPU baseline (rank 0, N=1), the 8-scene and training extras, the batch-1
+    latency probe."""
+    wl.events = []
+    for _ in range(5):
+        wl.step(timing=True)
+    torch.cuda.synchronize()
+    stages = {}
+    ev = wl.events
+    for (n0, e0), (n1, e1) in zip(ev[:-1], ev[1:]):
+        if n1 != "start":
+            stages[n1] = stages.get(n1, 0.0) + e0.elapsed_time(e1) / 5
+    collective = gather_evidence(wl, device) if world > 1 else None  # every rank takes part
+    torch.cuda.synchronize()
+    if rank == 0:
+        out["stage_ms"] = {k: round(v, 4) for k, v in stages.items()}
+        out["serial_ms_per_step"] = round(sum(stages.values()), 4)
+        # the same step with the two stages back to back on one stream (no pipelining credit)
+        out["value_serial"] = round(world * wl.B / (sum(stages.values()) / 1e3), 3) if stages else None
+        if collective is not None:
+            out["collective"] = dict(collective, backend="nccl (RCCL)")
+        t_vol, t_icc = handwritten_path(wl)
+        out["value_handwritten_path"] = round(world * wl.B / ((t_vol + t_icc) / 1e3), 3)
+        out["handwritten_path_ms"] = {"volumetric_network_part": round(t_vol, 4), "icc": round(t_icc, 4)}
+        out["roofline_conv4"] = roofline_conv4(wl, wl.B)
+        out["roofline_conv4_batch1"] = roofline_conv4(wl, 1)
+        out["roofline"] = roofline_icc(wl, t_icc * 1e3 / args.icc_iters)  # all scenes share the launches
+        out["roofline_voxelize"] = roofline_voxelize(wl)
+        out["roofline_bf16_kernels"] = roofline_bf16_kernels(wl)
+        lap("rooflines")
+        out["accuracy"] = accuracy(wl)
+        lap("accuracy")
+        if world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(wl, args)
+        torch.cuda.synchronize()
+        lap("cpu_baseline")
+        if world == 1 and not args.no_extras and args.scenes_per_gpu == 1:
+            # configs[3] / configs[4] per-GPU shares inside the driver-run line (round-4 verdict item 7)
+            try:  # (the extras must never take the headline line down)
+                s8 = extra_scenes8(args, rank, device)
+                out["value_scenes8"] = s8["value"]
+                out["scenes8"] = s8
+            except Exception as e:
+                out["scenes8"] = {"error": repr(e)[:200]}
+            lap("extra_scenes8")
+            tr = extra_training()
+            out["train_objects_per_s"] = tr.get("train_objects_per_s")
+            out["training"] = tr
+            lap("extra_training")
+            if time.perf_counter() - T_START < 150.0:  # the same step replayed from hipGraphs (--graph), time permitting
+                tg = extra_training(graph=True)
+                out["train_objects_per_s_hipgraph"] = tg.get("train_objects_per_s")
+                out["training_hipgraph"] = tg
+            torch.cuda.synchronize()
+        if not args.no_latency_probe:
+            out["latency_batch1_ms"] = latency_batch1(wl)  # child process, last: nothing of this one depends on it
+            lap("latency_probe")
+        # (where the wall time goes: MIOpen's solver search runs its candidates on the GPU for every new shape --
+        # ~12 s for the headline's B = 8, ~45 s for the 8-scene extra's B = 64, ~30 s for the training child)
 
 
 T_START = time.perf_counter()
@@ -874,34 +975,29 @@ def main():
             wl.step()
         torch.cuda.synchronize()
         wl.icc.prepare()
-    elapsed = parallel.timed_steps(wl.step, args.steps, 0 if mark else args.warmup, device=device)
+    last = {}
+
+    def step():  # keeps what the step hands its caller, for --dump-outputs
+        last["refined_poses"], last["network_poses"] = wl.step()
+
+    elapsed = parallel.timed_steps(step, args.steps, 0 if mark else args.warmup, device=device)
     if mark:
         wl.icc.prepare()
         torch.cuda.synchronize()
 
     lap("warmup_and_timed_steps")
-    # un-timed extras: stage breakdown, live kernel timing, CPU baseline (rank 0, N=1)
-    wl.events = []
-    for _ in range(5):
-        wl.step(timing=True)
-    torch.cuda.synchronize()
-    stages = {}
-    ev = wl.events
-    for (n0, e0), (n1, e1) in zip(ev[:-1], ev[1:]):
-        if n1 != "start":
-            stages[n1] = stages.get(n1, 0.0) + e0.elapsed_time(e1) / 5
     out = None
-    collective = gather_evidence(wl, device) if world > 1 else None  # every rank takes part
-    torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(last, **wl.last_predict))
+        lap("dump_outputs")
     if rank == 0:
         total_objects = world * wl.B * args.steps
-        ms_per_step = elapsed / args.steps * 1e3
         out = {
             "metric": "objects/sec (32^3 voxelize+3D-CNN+ICC refine)",
             "value": round(total_objects / elapsed, 3),
             "unit": "objects/sec",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": args.dtype, "data": "synthetic",
             "config": {
@@ -920,51 +1016,10 @@ def main():
                 "stream_priority": args.priority, "icc_cu_mask": args.icc_cus or None, "backbone_memory_format":
                     "channels_last" if args.channels_last else "contiguous",
             },
-            "stage_ms": {k: round(v, 4) for k, v in stages.items()},
-            "serial_ms_per_step": round(sum(stages.values()), 4),
-            # the same step with the two stages back to back on one stream (no pipelining credit)
-            "value_serial": round(world * wl.B / (sum(stages.values()) / 1e3), 3) if stages else None,
         }
-        if collective is not None:
-            out["collective"] = dict(collective, backend="nccl (RCCL)")
-        t_vol, t_icc = handwritten_path(wl)
-        out["value_handwritten_path"] = round(world * wl.B / ((t_vol + t_icc) / 1e3), 3)
-        out["handwritten_path_ms"] = {"volumetric_network_part": round(t_vol, 4), "icc": round(t_icc, 4)}
-        out["roofline_conv4"] = roofline_conv4(wl, wl.B)
-        out["roofline_conv4_batch1"] = roofline_conv4(wl, 1)
-        out["roofline"] = roofline_icc(wl, t_icc * 1e3 / args.icc_iters)  # all scenes share the launches
-        out["roofline_voxelize"] = roofline_voxelize(wl)
-        out["roofline_bf16_kernels"] = roofline_bf16_kernels(wl)
-        lap("rooflines")
-        out["accuracy"] = accuracy(wl)
-        lap("accuracy")
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(wl, args)
-        torch.cuda.synchronize()
-        lap("cpu_baseline")
-        if world == 1 and not args.no_extras and args.scenes_per_gpu == 1:
-            # configs[3] / configs[4] per-GPU shares inside the driver-run line (round-4 verdict item 7)
-            try:  # (the extras must never take the headline line down)
-                s8 = extra_scenes8(args, rank, device)
-                out["value_scenes8"] = s8["value"]
-                out["scenes8"] = s8
-            except Exception as e:
-                out["scenes8"] = {"error": repr(e)[:200]}
-            lap("extra_scenes8")
-            tr = extra_training()
-            out["train_objects_per_s"] = tr.get("train_objects_per_s")
-            out["training"] = tr
-            lap("extra_training")
-            if time.perf_counter() - T_START < 150.0:  # the same step replayed from hipGraphs (--graph), time permitting
-                tg = extra_training(graph=True)
-                out["train_objects_per_s_hipgraph"] = tg.get("train_objects_per_s")
-                out["training_hipgraph"] = tg
-            torch.cuda.synchronize()
-        if not args.no_latency_probe:
-            out["latency_batch1_ms"] = latency_batch1(wl)  # child process, last: nothing of this one depends on it
-            lap("latency_probe")
-        # (where the wall time goes: MIOpen's solver search runs its candidates on the GPU for every new shape --
-        # ~12 s for the headline's B = 8, ~45 s for the 8-scene extra's B = 64, ~30 s for the training child)
+    if args.full:
+        full_extras(args, wl, world, rank, device, out, lap)
+    if rank == 0:
         out["bench_wall_sections_s"] = walls
         out["bench_wall_s"] = round(time.perf_counter() - T_START, 1)  # this process, after the imports
         print(json.dumps(out))

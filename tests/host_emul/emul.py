@@ -49,7 +49,8 @@ def build(sources, extra_flags=()):
     tag = h.hexdigest()[:16]
     so = os.path.join(BUILD, f"libmfemul_{tag}.so")
     if not os.path.exists(so):
-        work = os.path.join(BUILD, tag)
+        # per-process work directory and an atomic rename: concurrent test processes may build the same tag
+        work = os.path.join(BUILD, f"{tag}.{os.getpid()}")
         os.makedirs(work, exist_ok=True)
         for hname in os.listdir(CSRC):  # shared device headers (the emulator's mf_common.h shadows csrc's)
             if hname.endswith(".h") and hname != "mf_common.h":
@@ -61,7 +62,9 @@ def build(sources, extra_flags=()):
             shutil.copy(os.path.join(CSRC, name), dst)
             cpps.append(dst)
         subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-w",
-                        "-I", os.path.join(ROOT, "include"), *extra_flags, "-o", so, *cpps], check=True)
+                        "-I", os.path.join(ROOT, "include"), *extra_flags, "-o", os.path.join(work, "lib.so"), *cpps],
+                       check=True)
+        os.replace(os.path.join(work, "lib.so"), so)
         shutil.rmtree(work, ignore_errors=True)
     return ctypes.CDLL(so)
 

@@ -8,6 +8,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -50,3 +52,27 @@ def test_bench_respects_an_external_launcher():
 def test_training_example_self_launches_two_ranks():
     out = _run(["examples/singleview_3d_train.py", "--gpus", "2", "--dry-run-cpu"])
     assert out["n_ranks"] == 2 and out["ranks_seen"] == [0, 1] and out["ddp_gradient_is_rank_mean"]
+
+
+def test_bench_dump_outputs_writes_the_last_step(tmp_path):
+    """`--dump-outputs DIR`: the arrays the last timed step handed its caller, as DIR/<name>.npy in float32."""
+    out = _run(["bench.py", "--steps", "2", "--warmup", "1", "--dry-run-cpu", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 2
+    poses = np.load(tmp_path / "poses.npy")
+    assert poses.dtype == np.float32 and poses.shape == (8, 7)
+    assert np.array_equal(poses, np.arange(8)[:, None] * 10.0 + np.arange(7)[None, :])  # the stub step's poses
+
+
+def test_bench_dump_outputs_samples_what_exceeds_the_limit(tmp_path, monkeypatch):
+    """Over the size limit an array becomes a fixed, seeded sample of its elements: the same one in every run."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    big = np.arange(10000, dtype=np.float64).reshape(100, 100)
+    small = np.ones((4, 7), np.float16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float64 and a.nbytes <= 2048 and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and set(a.tolist()) <= set(big.reshape(-1).tolist())
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (4, 7)

@@ -7,7 +7,7 @@ for v in "$@"; do
   n=$((n+1))
   envs=""; flags=$v
   case $v in *:*) envs=${v%%:*}; flags=${v#*:};; esac
-  env ${envs//,/ } timeout 600 python bench.py --steps 30 --no-extras --no-cpu-baseline --no-latency-probe ${flags//+/ } > "$O/bench_$n.json" 2> "$O/bench_$n.err"
+  env ${envs//,/ } timeout 600 python bench.py --full --steps 30 --no-extras --no-cpu-baseline --no-latency-probe ${flags//+/ } > "$O/bench_$n.json" 2> "$O/bench_$n.err"
   echo "[$v] rc $?"; python -c "
 import json,sys
 d=json.loads(open('$O/bench_$n.json').read().strip().splitlines()[-1])

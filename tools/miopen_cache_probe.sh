@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/$1; mkdir -p "$O/db"
 export MIOPEN_USER_DB_PATH=$PWD/$O/db
 for i in 1 2; do
-  t0=$(date +%s); timeout 900 python bench.py > "$O/bench_$i.json" 2> "$O/bench_$i.err"; echo "rc $? wall $(( $(date +%s) - t0 )) s"
+  t0=$(date +%s); timeout 900 python bench.py --full > "$O/bench_$i.json" 2> "$O/bench_$i.err"; echo "rc $? wall $(( $(date +%s) - t0 )) s"
   tail -n 1 "$O/bench_$i.err"
   python -c "
 import json
