@@ -640,6 +640,58 @@ int mf_instance_crops(const uint8_t *rgb, const float *depth, const int32_t *lab
 int mf_valid_pixel_order(const float *pcd, int32_t B, int32_t HW, int32_t *order, int32_t *counts,
                          mfStream_t stream);
 
+/* ---- occupancy mapping (contrib/multi_instance_octree_mapping.py, csrc/occmap.hip) ---------
+ * The reference's per-instance OctoMap (contrib.MultiInstanceOctreeMapping) as one dense float32
+ * log-odds volume per instance over a box of octree keys (key = floor(double(c) / pitch) + 32768
+ * per axis, c rounded to float32 first); NaN = never touched (unknown).  cell (kx, ky, kz) is
+ * element ((kx - lo[0]) * dim[1] + ky - lo[1]) * dim[2] + kz - lo[2] of `logodds`; `bits`
+ * [2 * cells] uint32 holds the per-scan free / occupied bits (or the hit counts of an update)
+ * between a ray-cast and the apply pass and is all-zero otherwise.
+ * `slots` [n_slots, 3] int32 = {label value, tree index, scan index (0..31)}: a point whose label
+ * matches a slot's value is one measurement of that tree's scan.  `trees` is a DEVICE array of
+ * mfOccTree; `pts` [n, 3] float32 (NaN rows are skipped), one sensor origin per launch.
+ * Every call is asynchronous, allocates nothing and never synchronises. */
+typedef struct {
+  float *logodds;
+  uint32_t *bits;
+  int32_t lo[3];
+  int32_t dim[3];
+  double resolution;
+  double res_factor; /* 1.0 / resolution */
+} mfOccTree;
+/* dst (HOST pointer to the descriptor) := src where the boxes overlap, NaN elsewhere; dst bits := 0.
+ * src may be NULL (a fresh box); src and dst must not alias. */
+int mf_occmap_regrid(const mfOccTree *src, const mfOccTree *dst, mfStream_t stream);
+/* bounds [n_trees, 6] int32 := per tree {min key x,y,z, max key x,y,z} over its measured points
+ * ({INT_MAX x3, INT_MIN x3} for a tree without points); n_trees <= 256. */
+int mf_occmap_bounds(const float *pts, const int32_t *label, int64_t n, const int32_t *slots,
+                     int32_t n_slots, const mfOccTree *trees, int32_t n_trees, int32_t *bounds,
+                     mfStream_t stream);
+/* octomap's insertPointCloud ray-cast: per point the DDA keys origin -> point set bit `scan` in
+ * the free word, the end key in the occupied word.  Keys outside a tree's box are dropped and
+ * counted in *overflow (may be NULL; the caller sizes the boxes so that this stays 0). */
+int mf_occmap_raycast(const float *pts, const int32_t *label, int64_t n, const int32_t *slots,
+                      int32_t n_slots, const mfOccTree *trees, float origin_x, float origin_y,
+                      float origin_z, int32_t *overflow, mfStream_t stream);
+/* update(): one hit per point of tree `tree` (no merging of duplicates): integer counts in the
+ * free word.  Keys outside the box are counted in *overflow (may be NULL). */
+int mf_occmap_count_hits(const float *pts, int64_t n, const mfOccTree *trees, int32_t tree,
+                         int32_t *overflow, mfStream_t stream);
+/* One lane per cell of every tree: mode 0 applies the scans in order (occupied bit -> hit, else
+ * free bit -> miss), mode 1 applies the hit counts; float32 adds with octomap's clamping, then
+ * the bits are cleared.  max_cells = the largest tree's cell count. */
+int mf_occmap_apply(const mfOccTree *trees, int32_t n_trees, int64_t max_cells, int32_t mode,
+                    mfStream_t stream);
+/* get_target_grids for B grids of D0 x D1 x D2 voxels: voxel centre origin[b] + i * pitch[b]
+ * (float64, then float32), trees visited in index order, occupancy 1 - 1 / (1 + exp(l)) in float64;
+ * grid_target / grid_nontarget / grid_empty [B, D0, D1, D2] float32 (last writer wins).
+ * target_tree [B] int32 (-1: none).  net_target / net_nte [B, D0, D1, D2] uint8 (both NULL or
+ * both set): grids_for_network(train=False) of the three grids. */
+int mf_occmap_extract(const mfOccTree *trees, int32_t n_trees, const int32_t *target_tree,
+                      const double *pitch, const double *origin, int32_t B, int32_t D0, int32_t D1,
+                      int32_t D2, float *grid_target, float *grid_nontarget, float *grid_empty,
+                      uint8_t *net_target, uint8_t *net_nte, mfStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

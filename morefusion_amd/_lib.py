@@ -35,6 +35,15 @@ class IccBatch(ctypes.Structure):
     ]
 
 
+class OccTree(ctypes.Structure):
+    """mfOccTree (include/mfhip.h)."""
+
+    _fields_ = [
+        ("logodds", _p), ("bits", _p), ("lo", ctypes.c_int32 * 3), ("dim", ctypes.c_int32 * 3),
+        ("resolution", _d), ("res_factor", _d),
+    ]
+
+
 _SIGNATURES = {
     "mf_version": ([], _i),
     "mf_last_error_string": ([], ctypes.c_char_p),
@@ -145,6 +154,12 @@ _SIGNATURES = {
     "mf_valid_pixel_order": ([_p, ctypes.c_int32, ctypes.c_int32, _p, _p, _p], _i),
     "mf_instance_stats": ([_p, _p, _i, _i, _p, _i, _p, _p], _i),
     "mf_instance_crops": ([_p, _p, _p, _i, _i, _d, _d, _d, _d, _p, _p, _i, _i, _i, _p, _p, _p, _p], _i),
+    "mf_occmap_regrid": ([ctypes.POINTER(OccTree), ctypes.POINTER(OccTree), _p], _i),
+    "mf_occmap_bounds": ([_p, _p, _i64, _p, ctypes.c_int32, _p, ctypes.c_int32, _p, _p], _i),
+    "mf_occmap_raycast": ([_p, _p, _i64, _p, ctypes.c_int32, _p, _f, _f, _f, _p, _p], _i),
+    "mf_occmap_count_hits": ([_p, _i64, _p, ctypes.c_int32, _p, _p], _i),
+    "mf_occmap_apply": ([_p, ctypes.c_int32, _i64, ctypes.c_int32, _p], _i),
+    "mf_occmap_extract": ([_p, ctypes.c_int32, _p, _p, _p] + [ctypes.c_int32] * 4 + [_p] * 6, _i),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -5,3 +5,4 @@ from .iterative_closest_point_link import IterativeClosestPointLink, icp_refine
 from .iterative_collision_check_link import IterativeCollisionCheckLink
 from .occupancy_registration import OccupancyRegistration, OccupancyRegistrationLink
 from . import singleview_3d
+from .multi_instance_octree_mapping import MultiInstanceOctreeMapping

@@ -303,3 +303,53 @@ def make_rgbd_frame(seed=0, height=480, width=640):
     K = np.array([[619.4, 0, width / 2 - 0.3], [0, 618.9, height / 2 + 0.7], [0, 0, 1]])
     ids = np.array([3, 5, 7, 11, 13, 17, 19, 23], np.int32)                            # 23 is absent
     return dict(rgb=rgb, depth=depth, K=K, label=label, instance_ids=ids)
+
+
+def make_occupancy_frame(seed=0, height=480, width=640, n_objects=8):
+    """A frame with real geometry for the occupancy-mapping row: spheres and boxes standing on a table
+    plane in front of a back wall, ray-traced analytically from a pinhole camera at the origin (looking
+    along +z, y down), so that free space and occlusion mean something.  The intrinsics scale with the
+    width (the same scene at any resolution).  Labels: 0 = wall, 1 = table (both background),
+    instance_ids[i] = object i.  Returns dict(rgb u8 [H,W,3], depth f32 [H,W] (NaN holes), K [3,3]
+    float64, label i32 [H,W], instance_ids i32 [n], class_ids i32 [n])."""
+    rs = np.random.RandomState(seed)
+    s = width / 640.0
+    K = np.array([[619.4 * s, 0, width / 2 - 0.3], [0, 618.9 * s, height / 2 + 0.7], [0, 0, 1]])
+    v, u = np.mgrid[:height, :width].astype(np.float64)
+    d = np.stack([(u - K[0, 2]) / K[0, 0], (v - K[1, 2]) / K[1, 1], np.ones_like(u)], -1)  # ray at z = 1
+    table_y, wall_z = 0.2, 1.4
+    t_best = np.full((height, width), wall_z)  # the wall: z = wall_z, t = z along a ray of unit z
+    label = np.zeros((height, width), np.int32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t_table = np.where(d[..., 1] > 0, table_y / d[..., 1], np.inf)
+    hit = t_table < t_best
+    t_best[hit], label[hit] = t_table[hit], 1
+    classes = sorted(CLASS_PITCH)
+    class_ids = rs.choice(classes, n_objects, replace=False).astype(np.int32)
+    instance_ids = np.arange(2, 2 + n_objects, dtype=np.int32)
+    dd = (d * d).sum(-1)
+    for i in range(n_objects):
+        x = -0.35 + 0.7 * (i + rs.uniform(0.2, 0.8)) / n_objects
+        z = rs.uniform(0.7, 1.15)
+        r = rs.uniform(0.03, 0.06)
+        if i % 2 == 0:  # sphere resting on the table
+            c = np.array([x, table_y - r, z])
+            b = (d * c).sum(-1)
+            disc = b * b - dd * (c @ c - r * r)
+            with np.errstate(invalid="ignore"):
+                t = np.where(disc >= 0, (b - np.sqrt(disc)) / dd, np.inf)
+        else:  # axis-aligned box standing on the table
+            lo = np.array([x - r, table_y - rs.uniform(1.0, 2.5) * r, z - r])
+            hi = np.array([x + r, table_y, z + r])
+            with np.errstate(divide="ignore", invalid="ignore"):
+                t1, t2 = lo / d, hi / d
+            tn = np.nanmax(np.minimum(t1, t2), -1)
+            tf = np.nanmin(np.maximum(t1, t2), -1)
+            t = np.where((tn <= tf) & (tf > 0), tn, np.inf)
+        hit = (t > 0) & (t < t_best)
+        t_best[hit], label[hit] = t[hit], instance_ids[i]
+    depth = t_best.astype(np.float32)  # z of the hit (the ray has unit z)
+    depth[rs.uniform(size=depth.shape) < 0.03] = np.nan
+    palette = rs.randint(0, 256, (2 + n_objects + 2, 3)).astype(np.uint8)
+    rgb = palette[np.clip(label, 0, len(palette) - 1)]
+    return dict(rgb=rgb, depth=depth, K=K, label=label, instance_ids=instance_ids, class_ids=class_ids)

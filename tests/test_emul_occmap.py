@@ -1,0 +1,110 @@
+"""csrc/occmap.hip through the host emulator (tests/host_emul) behind the product's Python layer
+(contrib/multi_instance_octree_mapping.py, torch CPU tensors as device memory): a small frame with real
+geometry -- 48 x 64 px, 3 foreground instances, 2 background labels -- mapped by integrate_frame, then two
+more integrates from another origin (the boxes grow) and an update(); every known key's log-odds and every
+target's three grids bitwise equal to the restatement (tests/occmap_ref.py)."""
+import numpy as np
+import pytest
+import torch
+
+import occmap_ref as R
+from host_emul import emul
+
+pytestmark = pytest.mark.skipif(not emul.available(), reason="g++ not available")
+
+ORIGIN2 = (0.05, -0.1, -0.08)
+
+
+@pytest.fixture()
+def M(monkeypatch):
+    from morefusion_amd import _lib
+    from morefusion_amd.contrib import multi_instance_octree_mapping as mod
+    L = emul.build(["occmap.hip"])
+    for name, (argtypes, restype) in _lib._SIGNATURES.items():
+        fn = getattr(L, name, None)
+        if fn is not None:
+            fn.argtypes, fn.restype = argtypes, restype
+    monkeypatch.setattr(_lib, "lib", lambda: L)
+    monkeypatch.setattr(_lib, "require_gpu", lambda *a: None)
+    monkeypatch.setattr(_lib, "stream_ptr", lambda: None)
+    monkeypatch.setattr(_lib, "check", lambda code, what: (_ for _ in ()).throw(RuntimeError(what)) if code else None)
+    return mod
+
+
+def _frame():
+    from morefusion_amd import geometry, synthetic
+    f = synthetic.make_occupancy_frame(1, 48, 64, n_objects=3)
+    K = f["K"]
+    pcd = geometry.pointcloud_from_depth(f["depth"], K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+    label = f["label"].copy()
+    label[label == 1] = 7  # background labels 0 (wall) and 7 (table)
+    return pcd, label, f["instance_ids"], f["class_ids"], (lambda c: synthetic.CLASS_PITCH[int(c)])
+
+
+def _logodds_equal(m, ref):
+    assert m.instance_ids == list(ref.octrees)
+    for iid in m.instance_ids:
+        lo, lg = m.dense_logodds(iid)
+        known = ~np.isnan(lg)
+        got = dict(zip(R.pack(np.argwhere(known) + lo).tolist(), lg[known].tolist()))
+        exp = ref.octrees[iid].values
+        assert set(got) == set(exp), (iid, len(set(got) ^ set(exp)))
+        assert all(np.float32(got[k]) == exp[k] for k in exp), iid
+
+
+def _grids_equal(m, ref, ids, cls, pcd, label, pitch_of):
+    for tid, c in zip(ids, cls):
+        p = pitch_of(c)
+        origin = np.nanmedian(pcd[label == tid], axis=0) - 15.5 * p  # base.py:153-163
+        got = m.get_target_grids(tid, dimensions=(32, 32, 32), pitch=p, origin=origin)
+        exp = ref.get_target_grids(tid, dimensions=(32, 32, 32), pitch=p, origin=origin)
+        for g, e in zip(got, exp):
+            assert g.dtype == np.float32 and np.array_equal(g, e), tid
+        assert (got[0] > 0).any() and (got[2] > 0).any()
+
+
+def test_frame_integrate_grow_update_bitwise_vs_restatement(M):
+    pcd, label, ids, cls, pitch_of = _frame()
+    m = M.MultiInstanceOctreeMapping(device="cpu")
+    m.integrate_frame(pcd, label, ids, cls, pitch_of)
+    ref = R.build_octomap(pcd, label, ids, cls, pitch_of)
+    _logodds_equal(m, ref)
+    _grids_equal(m, ref, ids, cls, pcd, label, pitch_of)
+
+    boxes = {i: m.dense_logodds(i)[1].shape for i in m.instance_ids}
+    for iid, mask in ((ids[0], label == ids[0]), (0, label == 7)):
+        m.integrate(iid, mask, pcd, origin=ORIGIN2)
+        ref.integrate(iid, mask, pcd, origin=ORIGIN2)
+    assert m.dense_logodds(ids[0])[1].shape != boxes[ids[0]] and m.dense_logodds(0)[1].shape != boxes[0]
+    occ = pcd[label == ids[1]][:6]
+    occ = np.concatenate([occ, occ[:2], occ[:1]])  # duplicates: one hit each
+    m.update(ids[1], occ)
+    ref.update(ids[1], occ)
+    _logodds_equal(m, ref)
+    _grids_equal(m, ref, ids, cls, pcd, label, pitch_of)
+    assert int(m._overflow[0]) == 0
+    for t in m._trees.values():
+        assert not t.bits.any()  # the apply pass leaves the scan bits cleared
+
+
+def test_network_inputs_and_tensor_inputs(M):
+    from morefusion_amd.data_formats import grids_for_network
+    pcd, label, ids, cls, pitch_of = _frame()
+    m = M.MultiInstanceOctreeMapping(device="cpu")
+    m.integrate_frame(pcd, label, ids, cls, pitch_of)
+    mt = M.MultiInstanceOctreeMapping(device="cpu")
+    mt.integrate_frame(torch.from_numpy(pcd), torch.from_numpy(label), ids, cls, pitch_of)
+    pitch = np.array([pitch_of(c) for c in cls])
+    origin = np.stack([np.nanmedian(pcd[label == i], axis=0) for i in ids]) - 15.5 * pitch[:, None]
+    gt, gn, ge, nt, nte = m.get_target_grids_batch(ids, pitch, origin, network_inputs=True)
+    for b in range(len(ids)):
+        t_ref, nte_ref = grids_for_network(gt[b], gn[b], ge[b], train=False)
+        assert np.array_equal(nt[b], t_ref) and np.array_equal(nte[b], nte_ref)
+    got_t = mt.get_target_grids_batch(torch.as_tensor(ids), torch.from_numpy(pitch), torch.from_numpy(origin))
+    assert all(isinstance(g, torch.Tensor) for g in got_t)
+    for a, b in zip(got_t, (gt, gn, ge)):
+        assert np.array_equal(a.numpy(), b)
+    with pytest.raises(NotImplementedError):
+        m.get_target_pcds(ids[0])
+    with pytest.raises(ValueError):
+        m.initialize(ids[0], pitch=0.01)
