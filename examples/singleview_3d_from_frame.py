@@ -8,7 +8,12 @@ instance crops (HIP, no host loop) -> grid placement -> Model.predict -> arg-max
 geometry (synthetic.make_occupancy_frame), full-frame back-projection uploaded to the device ->
 MultiInstanceOctreeMapping.integrate_frame -> per-object grids at the network's origin / class pitch ->
 Model.predict with the real grid_nontarget_empty -> ICC refinement (IccScenes) on grid_target /
-grid_nontarget_empty."""
+grid_nontarget_empty.
+
+``--icp``: the node's ICP refinement (singleview_3d_pose_estimation.py:236-262) on top of either path: the
+arg-max pose's transformation_matrix as the init, every kept instance's valid crop points against a CAD
+stand-in cloud (synthetic.make_primitive of the class pitch), objects below ``--confidence`` skipped through
+``active`` -- one contrib.icp_registration_batch call, no host loop over objects."""
 import argparse
 import os
 import sys
@@ -27,6 +32,8 @@ def main():
     ap.add_argument("--occupancy", action="store_true",
                     help="map the frame's occupancy, feed it to the network and refine the poses with ICC")
     ap.add_argument("--icc-iters", type=int, default=30)
+    ap.add_argument("--icp", action="store_true", help="refine the arg-max poses with ICPRegistration (batched)")
+    ap.add_argument("--confidence", type=float, default=0.0, help="--icp: objects below this confidence are skipped")
     args = ap.parse_args()
     if args.occupancy:
         return main_occupancy(args)
@@ -56,6 +63,8 @@ def main():
     T = morefusion.functions.transformation_matrix(quaternion[ar, best], translation[ar, best])
     for ins, cls, t in zip(instance_ids, class_id.tolist(), T.cpu().numpy()):
         print(f"instance {ins} (class {cls}): translation {np.round(t[:3, 3], 4)}")
+    if args.icp:
+        return refine_icp(pcd, quaternion, translation, confidence, class_id, instance_ids, args.confidence)
 
 
 def main_occupancy(args):
@@ -120,7 +129,36 @@ def main_occupancy(args):
     print(f"ICC loss {float(losses[0, 0]):.6f} -> {float(losses[-1, 0]):.6f} in {args.icc_iters} iterations")
     for ins, cls, tr in zip(instance_ids, class_id.tolist(), T.cpu().numpy()):
         print(f"instance {ins} (class {cls}): translation {np.round(tr[:3, 3], 4)}")
+    if args.icp:
+        refine_icp(pcd, quaternion, translation, confidence, class_id, instance_ids, args.confidence)
     return dict(grid_nontarget_empty=grid_nontarget_empty, losses=losses, transform=T)
+
+
+def cad_standin(class_id):
+    """A CAD stand-in cloud per class: the surface layer of a solid primitive of the class pitch."""
+    from morefusion_amd.contrib.singleview_3d.models.model import PitchTableModels
+    pitch = PitchTableModels().get_voxel_pitch(32, int(class_id))
+    p, d = morefusion.synthetic.make_primitive("box" if int(class_id) % 2 else "sphere", pitch,
+                                               np.random.RandomState(int(class_id)))
+    return p[d < pitch]
+
+
+def refine_icp(pcd, quaternion, translation, confidence, class_id, instance_ids, threshold, iteration=100):
+    """The node's ICP step for every kept instance in one batch: arg-max pose -> transformation_matrix (init) ->
+    icp_registration_batch(crop points [n, S, S, 3] with NaN holes, CAD stand-ins, active = confidence >= threshold)."""
+    best = confidence.argmax(dim=1)
+    ar = torch.arange(len(instance_ids), device=best.device)
+    T = morefusion.functions.transformation_matrix(quaternion[ar, best], translation[ar, best])
+    conf = confidence[ar, best]
+    classes = class_id.tolist()
+    transform, fitness, rmse, n_iter, hist = morefusion.contrib.icp_registration_batch(
+        pcd, [cad_standin(c) for c in classes], T.double(), iteration=iteration, voxel_size=0.01,
+        active=conf >= threshold, return_history=True, cad_keys=classes)
+    for ins, c, f, r, n, ok in zip(instance_ids, conf.tolist(), fitness.tolist(), rmse.tolist(), n_iter.tolist(),
+                                   (conf >= threshold).tolist()):
+        state = f"fitness {f:.4f} inlier_rmse {r:.6f} iterations {n}" if ok else "skipped"
+        print(f"icp instance {ins} (confidence {c:.3f}): {state}")
+    return dict(init=T, transform=transform, fitness=fitness, inlier_rmse=rmse, n_iter=n_iter, history=hist)
 
 
 if __name__ == "__main__":

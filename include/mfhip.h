@@ -692,6 +692,73 @@ int mf_occmap_extract(const mfOccTree *trees, int32_t n_trees, const int32_t *ta
                       int32_t D2, float *grid_target, float *grid_nontarget, float *grid_empty,
                       uint8_t *net_target, uint8_t *net_nte, mfStream_t stream);
 
+/* ---- point-to-point ICP registration (contrib/icp_registration.py, csrc/icpreg.hip) ---------
+ * open3d's voxel_down_sample + registration_icp(PointToPoint, no scaling), restated in float64
+ * (DESIGN.md "ICP registration").  Point sets are packed double [n, 3] rows with int64 [n_sets + 1]
+ * row offsets; rows with a NaN coordinate are dropped.  Every call is asynchronous, allocates
+ * nothing and never synchronises. */
+#define MF_ICPREG_MAX_CELLS (1 << 24) /* voxel-box cells (and grid cells) of one prepare call */
+/* Host-only: bytes of `workspace` for mf_icpreg_prepare; < 0 past MF_ICPREG_MAX_CELLS. */
+int64_t mf_icpreg_workspace_bytes(int64_t total_cells, int64_t total_grid, int64_t n_points);
+/* Per set: vmin [n_sets, 3] = min of the valid rows - voxel_size / 2; ext [n_sets, 4] int32 =
+ * {nx, ny, nz, n_valid}, nx = floor((max - vmin) / voxel_size) + 1 (-1: too large; all 0 for a set
+ * without valid rows).  The caller reads ext back to size the boxes. */
+int mf_icpreg_bounds(const double *pts, const int64_t *off, int32_t n_sets, double voxel_size,
+                     double *vmin, int32_t *ext, mfStream_t stream);
+/* voxel_down_sample of every set: out (packed like pts) rows off[b] .. off[b] + out_cnt[b] are the
+ * voxel means (input-order float64 sums / count) in (i, j, k) lexicographic voxel order.
+ * box_off [n_sets + 1] int64 = prefix of nx * ny * nz (total_cells).  A set b with grid_off[b + 1] >
+ * grid_off[b] is also binned into a uniform grid of cell `cell`, dims grid_dim[b] (int32 [n_sets, 3]),
+ * origin grid_origin[b] := vmin[b] - cell: grid_start[grid_off[b] ..] holds G + 1 starts into
+ * grid_idx (rows relative to the set, at its rows off[b] ..), each cell's rows ascending. */
+int mf_icpreg_prepare(const double *pts, const int64_t *off, int32_t n_sets, double voxel_size,
+                      const double *vmin, const int32_t *ext, const int64_t *box_off,
+                      int64_t total_cells, const int64_t *grid_off, const int32_t *grid_dim,
+                      int64_t total_grid, double cell, int64_t n_points, void *workspace,
+                      double *out, int32_t *out_cnt, double *grid_origin, int32_t *grid_start,
+                      int32_t *grid_idx, mfStream_t stream);
+/* One ICP problem per object (all DEVICE pointers).  Object b: source rows src_off[b] ..
+ * + src_cnt[b] of src, target rows tgt_off[b] .. + tgt_cnt[b] of tgt with its grid at
+ * grid_start + grid_off[b], grid_dim[b], grid_origin[b] (objects may share a target).
+ * transform_init [B, 16] cad -> cam (row-major); active [B] uint8 (NULL: all).  cur [src rows, 3]
+ * and corr [src rows] are workspace.  Outputs: transform [B, 16] (cad -> cam), transformation
+ * [B, 16] (depth -> cad), fitness, inlier_rmse [B], n_iter [B]; optional history (all three or
+ * none) [B, max_iter + 1, 16] / [B, max_iter + 1]: entry 0 = transform_init and the result there,
+ * entry k = after update k, entries past n_iter repeat the last.  mode 0 = register (stop when
+ * |d fitness| and |d rmse| < 1e-6), mode 1 = register_iterative (max_iter one-update steps). */
+typedef struct {
+  const double *src;
+  const int64_t *src_off;
+  const int32_t *src_cnt;
+  const double *tgt;
+  const int64_t *tgt_off;
+  const int32_t *tgt_cnt;
+  const int64_t *grid_off;
+  const int32_t *grid_dim;
+  const double *grid_origin;
+  const int32_t *grid_start;
+  const int32_t *grid_idx;
+  const double *transform_init;
+  const uint8_t *active;
+  double *cur;
+  int32_t *corr;
+  double *transform;
+  double *transformation;
+  double *fitness;
+  double *inlier_rmse;
+  int32_t *n_iter;
+  double *hist_transform;
+  double *hist_fitness;
+  double *hist_rmse;
+  double max_corr_dist;
+  double cell;
+  int32_t n_objects;
+  int32_t max_iter;
+  int32_t mode;
+  int32_t reserved;
+} mfIcpRegBatch;
+int mf_icpreg_run(const mfIcpRegBatch *batch, mfStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,17 @@ class OccTree(ctypes.Structure):
     ]
 
 
+class IcpRegBatch(ctypes.Structure):
+    """mfIcpRegBatch (include/mfhip.h)."""
+
+    _fields_ = [(n, _p) for n in (
+        "src", "src_off", "src_cnt", "tgt", "tgt_off", "tgt_cnt", "grid_off", "grid_dim", "grid_origin", "grid_start",
+        "grid_idx", "transform_init", "active", "cur", "corr", "transform", "transformation", "fitness", "inlier_rmse",
+        "n_iter", "hist_transform", "hist_fitness", "hist_rmse")] + [
+        ("max_corr_dist", _d), ("cell", _d), ("n_objects", ctypes.c_int32), ("max_iter", ctypes.c_int32),
+        ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 _SIGNATURES = {
     "mf_version": ([], _i),
     "mf_last_error_string": ([], ctypes.c_char_p),
@@ -160,6 +171,10 @@ _SIGNATURES = {
     "mf_occmap_count_hits": ([_p, _i64, _p, ctypes.c_int32, _p, _p], _i),
     "mf_occmap_apply": ([_p, ctypes.c_int32, _i64, ctypes.c_int32, _p], _i),
     "mf_occmap_extract": ([_p, ctypes.c_int32, _p, _p, _p] + [ctypes.c_int32] * 4 + [_p] * 6, _i),
+    "mf_icpreg_workspace_bytes": ([_i64, _i64, _i64], _i64),
+    "mf_icpreg_bounds": ([_p, _p, ctypes.c_int32, _d, _p, _p, _p], _i),
+    "mf_icpreg_prepare": ([_p, _p, ctypes.c_int32, _d, _p, _p, _p, _i64, _p, _p, _i64, _d, _i64] + [_p] * 7, _i),
+    "mf_icpreg_run": ([ctypes.POINTER(IcpRegBatch), _p], _i),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

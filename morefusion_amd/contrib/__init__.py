@@ -6,3 +6,4 @@ from .iterative_collision_check_link import IterativeCollisionCheckLink
 from .occupancy_registration import OccupancyRegistration, OccupancyRegistrationLink
 from . import singleview_3d
 from .multi_instance_octree_mapping import MultiInstanceOctreeMapping
+from .icp_registration import ICPRegistration, icp_registration_batch

@@ -353,3 +353,44 @@ def make_occupancy_frame(seed=0, height=480, width=640, n_objects=8):
     palette = rs.randint(0, 256, (2 + n_objects + 2, 3)).astype(np.uint8)
     rgb = palette[np.clip(label, 0, len(palette) - 1)]
     return dict(rgb=rgb, depth=depth, K=K, label=label, instance_ids=instance_ids, class_ids=class_ids)
+
+
+def _euler_pose(ang, t):
+    T = np.eye(4)
+    T[:3, :3] = random_rotation_from_euler(ang)
+    T[:3, 3] = t
+    return T
+
+
+def random_rotation_from_euler(ang):
+    cx, cy, cz = np.cos(ang)
+    sx, sy, sz = np.sin(ang)
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return Rz @ Ry @ Rx
+
+
+def make_icp_batch(n, seed=0, n_cad=600, noise=0.001, max_angle=0.05, max_shift=0.006):
+    """n ICP problems (contrib.icp_registration_batch): a CAD stand-in (points on a box surface), its observation
+    (the camera-facing part under a random pose, ``noise`` m per point, 5 NaN rows mixed in) and an init pose
+    perturbed in the object frame by up to ``max_angle`` rad and ``max_shift`` m per axis (<= 5 deg / 1 cm).  -> (depth list, cad list, init [n, 4, 4],
+    ground truth [n, 4, 4]), all float64 cad -> camera."""
+    rs = np.random.RandomState(seed)
+    depth, cad, init, gt = [], [], [], []
+    for _ in range(n):
+        half = rs.uniform(0.03, 0.06, 3)
+        p = rs.uniform(-1, 1, (n_cad, 3)) * half
+        ax = rs.randint(0, 3, n_cad)
+        p[np.arange(n_cad), ax] = np.sign(rs.uniform(-1, 1, n_cad)) * half[ax]
+        T = _euler_pose(rs.uniform(-np.pi, np.pi, 3), rs.uniform(-0.2, 0.2, 3) + [0, 0, 0.6])
+        obs = p @ T[:3, :3].T + T[:3, 3]
+        normal_z = (np.eye(3)[ax] * np.sign(p[np.arange(n_cad), ax])[:, None]) @ T[:3, :3].T
+        obs = obs[normal_z[:, 2] < 0] + rs.normal(0, noise, (int((normal_z[:, 2] < 0).sum()), 3))
+        obs = np.concatenate([obs, np.full((5, 3), np.nan)])[rs.permutation(len(obs) + 5)]
+        d = _euler_pose(rs.uniform(-max_angle, max_angle, 3), rs.uniform(-max_shift, max_shift, 3))
+        depth.append(obs)
+        cad.append(p)
+        init.append(T @ d)
+        gt.append(T)
+    return depth, cad, np.stack(init), np.stack(gt)
