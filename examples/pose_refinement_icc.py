@@ -4,7 +4,9 @@ examples/ycb_video/pose_refinement/check_iterative_collision_check_link.py:14-79
 (same argument marshalling, hyper-parameters and iteration count; no viewer).
 
 Inputs: the three real fixture instances the reference ships (tests/golden/) plus
-synthetic primitives; their SDF values are synthetic (the YCB SDFs are a download).
+synthetic primitives; their SDF values are synthetic (the YCB SDFs are a download), or with
+--cad-dir DIR the fixture objects' (points, sdf) come from YCBVideoModels(DIR).get_sdf (the CAD meshes'
+solid points and signed distances, computed on the device).
   --mode step   : the reference's loop (loss.backward(); optimizer.update(); zerograds())
   --mode fused  : link.refine() -- the whole loop as one hipGraph on the device
 """
@@ -25,11 +27,20 @@ def main():
     ap.add_argument("--mode", choices=["step", "fused"], default="fused")
     ap.add_argument("--objects", type=int, default=8)
     ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--cad-dir", help="YCB-Video model directory (<NNN_name>/textured*.obj): the fixture objects' "
+                    "points and SDF from the CAD meshes instead of the synthetic stand-in")
     args = ap.parse_args()
 
     gold = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
     fixtures = [dict(np.load(os.path.join(gold, f"fixture_pose_refinement_0000000{i}.npz"))) for i in range(3)]
     data = morefusion.synthetic.make_icc_scene(args.objects, seed=0, fixtures=fixtures)
+    if args.cad_dir:  # the scene's first objects are the fixtures, in order
+        n_fix = min(len(fixtures), args.objects)
+        ycb = morefusion.datasets.YCBVideoModels(args.cad_dir)
+        for k, (p, d) in enumerate(ycb.get_sdf_batch([int(f["class_id"]) for f in fixtures[:n_fix]])):
+            data["points"][k], data["sdf"][k] = p.astype(np.float32), d.astype(np.float32)
+            print(f"object {k}: class {ycb.class_names[int(fixtures[k]['class_id'])]}, {len(p)} CAD points, "
+                  f"sdf {d.min():.4f} .. {d.max():.4f}")
 
     to_gpu = lambda x: torch.as_tensor(np.ascontiguousarray(x)).cuda()  # noqa: E731
     points = [to_gpu(p) for p in data["points"]]

@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--icc-iters", type=int, default=30)
     ap.add_argument("--icp", action="store_true", help="refine the arg-max poses with ICPRegistration (batched)")
     ap.add_argument("--confidence", type=float, default=0.0, help="--icp: objects below this confidence are skipped")
+    ap.add_argument("--cad-dir", help="YCB-Video model directory (<NNN_name>/textured*.obj): real CAD clouds for --icp "
+                    "and real (points, sdf) for --occupancy's ICC in place of the primitive stand-ins")
     args = ap.parse_args()
     if args.occupancy:
         return main_occupancy(args)
@@ -64,7 +66,8 @@ def main():
     for ins, cls, t in zip(instance_ids, class_id.tolist(), T.cpu().numpy()):
         print(f"instance {ins} (class {cls}): translation {np.round(t[:3, 3], 4)}")
     if args.icp:
-        return refine_icp(pcd, quaternion, translation, confidence, class_id, instance_ids, args.confidence)
+        return refine_icp(pcd, quaternion, translation, confidence, class_id, instance_ids, args.confidence,
+                          cad_cloud=cad_from_dir(args.cad_dir) if args.cad_dir else cad_standin)
 
 
 def main_occupancy(args):
@@ -109,10 +112,16 @@ def main_occupancy(args):
     q = quaternion[ar, best].float().contiguous()
     t = translation[ar, best].float().contiguous()
 
-    # ICC on the mapped grids; stand-in CAD points / SDFs (solid primitives of the class pitch)
+    # ICC on the mapped grids; stand-in CAD points / SDFs (solid primitives of the class pitch), or with --cad-dir the
+    # CAD models' solid points and signed distances (YCBVideoModels.get_sdf)
     rs = np.random.RandomState(0)
     points, sdf = [], []
-    for k, c in enumerate(class_id.tolist()):
+    if args.cad_dir:
+        ycb = morefusion.datasets.YCBVideoModels(args.cad_dir)
+        for p, d in ycb.get_sdf_batch(class_id.tolist()):
+            points.append(to_gpu(p.astype(np.float32)))
+            sdf.append(to_gpu(d.astype(np.float32)))
+    for k, c in enumerate(class_id.tolist()[len(points):]):
         p, d = morefusion.synthetic.make_primitive("sphere" if k % 2 == 0 else "box", models.get_voxel_pitch(32, c), rs)
         points.append(to_gpu(p))
         sdf.append(to_gpu(d))
@@ -130,7 +139,8 @@ def main_occupancy(args):
     for ins, cls, tr in zip(instance_ids, class_id.tolist(), T.cpu().numpy()):
         print(f"instance {ins} (class {cls}): translation {np.round(tr[:3, 3], 4)}")
     if args.icp:
-        refine_icp(pcd, quaternion, translation, confidence, class_id, instance_ids, args.confidence)
+        refine_icp(pcd, quaternion, translation, confidence, class_id, instance_ids, args.confidence,
+                   cad_cloud=cad_from_dir(args.cad_dir) if args.cad_dir else cad_standin)
     return dict(grid_nontarget_empty=grid_nontarget_empty, losses=losses, transform=T)
 
 
@@ -143,16 +153,30 @@ def cad_standin(class_id):
     return p[d < pitch]
 
 
-def refine_icp(pcd, quaternion, translation, confidence, class_id, instance_ids, threshold, iteration=100):
+def cad_from_dir(root):
+    """--cad-dir: the class's points.xyz when present, else its solid points (YCBVideoModels.get_sdf)."""
+    ycb = morefusion.datasets.YCBVideoModels(root)
+
+    def cad(class_id):
+        if ycb.get_pcd_file(class_id).exists():
+            return ycb.get_pcd(class_id)
+        return ycb.get_sdf(class_id)[0]
+    return cad
+
+
+def refine_icp(pcd, quaternion, translation, confidence, class_id, instance_ids, threshold, iteration=100,
+               cad_cloud=None):
     """The node's ICP step for every kept instance in one batch: arg-max pose -> transformation_matrix (init) ->
-    icp_registration_batch(crop points [n, S, S, 3] with NaN holes, CAD stand-ins, active = confidence >= threshold)."""
+    icp_registration_batch(crop points [n, S, S, 3] with NaN holes, CAD clouds (``cad_cloud(class_id)``, default the
+    stand-ins), active = confidence >= threshold)."""
+    cad_cloud = cad_cloud or cad_standin
     best = confidence.argmax(dim=1)
     ar = torch.arange(len(instance_ids), device=best.device)
     T = morefusion.functions.transformation_matrix(quaternion[ar, best], translation[ar, best])
     conf = confidence[ar, best]
     classes = class_id.tolist()
     transform, fitness, rmse, n_iter, hist = morefusion.contrib.icp_registration_batch(
-        pcd, [cad_standin(c) for c in classes], T.double(), iteration=iteration, voxel_size=0.01,
+        pcd, [cad_cloud(c) for c in classes], T.double(), iteration=iteration, voxel_size=0.01,
         active=conf >= threshold, return_history=True, cad_keys=classes)
     for ins, c, f, r, n, ok in zip(instance_ids, conf.tolist(), fitness.tolist(), rmse.tolist(), n_iter.tolist(),
                                    (conf >= threshold).tolist()):

@@ -759,6 +759,44 @@ typedef struct {
 } mfIcpRegBatch;
 int mf_icpreg_run(const mfIcpRegBatch *batch, mfStream_t stream);
 
+/* ---- mesh signed distance / solid voxelization (geometry/mesh_sdf.py, csrc/meshsdf.hip) -------
+ * M triangle meshes and one segment of queries per mesh, float64 throughout (DESIGN.md "CAD model
+ * preparation").  Per query: unsigned distance to the nearest face (Ericson's closest point), the
+ * arg-min face (lowest index on a tie), the generalized winding number w (Van Oosterom-Strackee solid
+ * angles summed in face-index order / 4 pi) and sdf = +d inside, -d outside, inside := w >= 0.5 or
+ * d <= 1e-8.  Every call is asynchronous, allocates nothing and never synchronises. */
+#define MF_MESHSDF_MAX_MESHES 65535
+#define MF_MESHSDF_MAX_FACES (1LL << 26)
+#define MF_MESHSDF_MAX_GRID_DIM 1024
+typedef struct {
+  const double *vertices;     /* packed [V, 3] */
+  const int64_t *v_off;       /* [M + 1] vertex row offsets */
+  const int32_t *faces;       /* packed [F, 3], indices local to the mesh (outside it: the face is skipped) */
+  const int64_t *f_off;       /* [M + 1] face row offsets */
+  double *face_rec;           /* workspace [F, 16]: written by mf_meshsdf_prepare, read by mf_meshsdf_query */
+  const double *points;       /* packed [Q, 3] queries; NULL: grid queries (below) */
+  const int64_t *q_off;       /* [M + 1] query offsets (grid queries: m * grid_dim^3) */
+  const int32_t *blk_off;     /* [M + 1] workgroup offsets: blk_off[m + 1] - blk_off[m] = ceil(queries of m / 256) */
+  const double *grid_origin;  /* [M, 3] grid queries: centre (i, j, k) = origin + (idx + 0.5) * grid_h[m] */
+  const double *grid_h;       /* [M] cell size */
+  double *dist;               /* [Q] outputs, each optional (NULL) */
+  int32_t *face;
+  double *winding;
+  double *sdf;
+  uint8_t *occupancy;         /* points: inside; grid: w >= 0.5 or d <= grid_h[m] / 2 */
+  int32_t n_meshes;
+  int32_t n_blocks;           /* blk_off[M] */
+  int32_t grid_dim;           /* grid queries: cells per axis */
+  int32_t reserved;
+} mfMeshSdfBatch;
+/* Host-only: bytes of face_rec for total_faces faces; < 0 past MF_MESHSDF_MAX_FACES. */
+int64_t mf_meshsdf_workspace_bytes(int64_t total_faces);
+/* Per-face records (vertices, edges, kind) of every mesh into face_rec; reads vertices, v_off, faces,
+ * f_off (total_faces = f_off[M]). */
+int mf_meshsdf_prepare(const mfMeshSdfBatch *batch, int64_t total_faces, mfStream_t stream);
+/* One lane per query over every face of its mesh; face_rec as prepared. */
+int mf_meshsdf_query(const mfMeshSdfBatch *batch, mfStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,3 +18,4 @@ from . import synthetic
 from . import data_formats
 from . import serializers
 from . import training
+from . import datasets

@@ -55,6 +55,16 @@ class IcpRegBatch(ctypes.Structure):
         ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class MeshSdfBatch(ctypes.Structure):
+    """mfMeshSdfBatch (include/mfhip.h)."""
+
+    _fields_ = [(n, _p) for n in (
+        "vertices", "v_off", "faces", "f_off", "face_rec", "points", "q_off", "blk_off", "grid_origin", "grid_h",
+        "dist", "face", "winding", "sdf", "occupancy")] + [
+        ("n_meshes", ctypes.c_int32), ("n_blocks", ctypes.c_int32), ("grid_dim", ctypes.c_int32),
+        ("reserved", ctypes.c_int32)]
+
+
 _SIGNATURES = {
     "mf_version": ([], _i),
     "mf_last_error_string": ([], ctypes.c_char_p),
@@ -175,6 +185,9 @@ _SIGNATURES = {
     "mf_icpreg_bounds": ([_p, _p, ctypes.c_int32, _d, _p, _p, _p], _i),
     "mf_icpreg_prepare": ([_p, _p, ctypes.c_int32, _d, _p, _p, _p, _i64, _p, _p, _i64, _d, _i64] + [_p] * 7, _i),
     "mf_icpreg_run": ([ctypes.POINTER(IcpRegBatch), _p], _i),
+    "mf_meshsdf_workspace_bytes": ([_i64], _i64),
+    "mf_meshsdf_prepare": ([ctypes.POINTER(MeshSdfBatch), _i64, _p], _i),
+    "mf_meshsdf_query": ([ctypes.POINTER(MeshSdfBatch), _p], _i),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -1,0 +1,3 @@
+# flake8: noqa
+# the CAD-model side of morefusion/datasets: models whose meshes are on disk (nothing is downloaded)
+from .ycb_video import YCBVideoModels
