@@ -417,6 +417,23 @@ int64_t mf_conv3d_bf16_fwd_workspace_bytes(int32_t B, int32_t Cin, int32_t Cout,
 int mf_conv3d_bf16_fwd_ws(const void *x, const void *wt, const float *bias, void *out, void *ws, int64_t ws_bytes,
                           int32_t B, int32_t Cin, int32_t Cout, int32_t D, int32_t ks, int32_t stride, int32_t pad,
                           int32_t dil, int32_t relu, int32_t out_f32, int32_t ldo, mfStream_t stream);
+/* 2-D convolutions of the inference backbone (models/backbone2d.py) as split-bf16 GEMMs on the NT engine: an fp32 value
+ * is carried as hi = bf16(x), lo = bf16(x - hi) and a product as hi w_hi + lo w_hi + hi w_lo, accumulated in fp32
+ * (relative error per product <= ~3 * 2^-18).  Kernel 1 or 3, stride 1 or 2, dilation 1 .. 4, any pad, output side
+ * Do a power of two; Cin, Cout % 8 == 0.
+ * mf_conv2d_split_pack   W fp32 [Cout][Cin][ks][ks] -> wp bf16 [Cout][ks^2][3 Cin] = [w_hi | w_hi | w_lo] per tap
+ * mf_conv2d_split_fwd    xs bf16 [B][D][D][2 Cin] (hi channels, then lo channels); row m = (b, oy, ox):
+ *                        v = act(conv + bias + res[m * ldr ..])  act 0 none, 1 ReLU, 2 PReLU with the slope *slope
+ *                        out32[m * ldo32 + n] = v and / or outs[m * ldos + n] = hi(v), outs[m * ldos + los + n] = lo(v)
+ *                        (null outputs / bias / res are skipped; pitches multiples of 8, operands 16-byte aligned);
+ *                        ws: mf_conv2d_split_workspace_bytes(...) bytes of split-K slabs (0: none needed) */
+int mf_conv2d_split_pack(const float *W, int32_t Cout, int32_t Cin, int32_t ks, void *wp, mfStream_t stream);
+int64_t mf_conv2d_split_workspace_bytes(int32_t B, int32_t Cin, int32_t Cout, int32_t D, int32_t ks, int32_t stride,
+                                        int32_t pad, int32_t dil);
+int mf_conv2d_split_fwd(const void *xs, const void *wp, const float *bias, const float *res, int32_t ldr,
+                        const float *slope, int32_t act, float *out32, int32_t ldo32, void *outs, int32_t ldos,
+                        int32_t los, void *ws, int64_t ws_bytes, int32_t B, int32_t Cin, int32_t Cout, int32_t D,
+                        int32_t ks, int32_t stride, int32_t pad, int32_t dil, mfStream_t stream);
 /* 3 x 3 x 3, stride 1, pad = dilation convolutions between NARROW layers (read channels 8 or 16, written channels <= 16)
  * on channels-last bf16 grids -- the occupancy branch conv1_occ / conv2_occ (model.py:69-72,120-124) and conv2_occ's
  * data gradient (pack with transpose = 1): voxels are the MFMA's columns, operands straight from global memory.
@@ -517,6 +534,13 @@ int mf_interpolate_voxel_grid_cl_bf16_bwd(const void *gout, int64_t ldg, const f
  *   mf_prelu_fwd / mf_prelu_bwd  y = x > 0 ? x : a x;  dx and dslope[0] = sum_{x <= 0} dy x (ws: mf_prelu_bwd_workspace_floats) */
 int mf_upsample_bilinear_cl_fwd(const void *x, void *y, int32_t B, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
                                 int32_t C, int32_t bf16, mfStream_t stream);
+/* the split-bf16 operand of mf_conv2d_split_fwd (hi at channel c, lo at channel los + c of rows of pitch ldy):
+ *   mf_upsample_bilinear_cl_split_fwd  the resize of fp32 x [B, H, W, C] (channels-last), taken in fp32, then split
+ *   mf_split_bf16                      fp32 x [B, C, H, W] at element strides (sb, sc, sh, sw), split */
+int mf_upsample_bilinear_cl_split_fwd(const float *x, void *y, int32_t B, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
+                                      int32_t C, int32_t ldy, int32_t los, mfStream_t stream);
+int mf_split_bf16(const float *x, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int32_t B, int32_t C, int32_t H,
+                  int32_t W, void *y, int32_t ldy, int32_t los, mfStream_t stream);
 int mf_upsample_bilinear_cl_bwd(const void *gy, void *gx, int32_t B, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
                                 int32_t C, int32_t bf16, mfStream_t stream);
 /* ... and for channels-first tensors [B*C, H, W] (one lane per element) */

@@ -122,6 +122,10 @@ _SIGNATURES = {
     "mf_conv3d_bf16_fwd": ([_p, _p, _p, _p] + [ctypes.c_int32] * 11 + [_p], _i),
     "mf_conv3d_bf16_fwd_workspace_bytes": ([ctypes.c_int32] * 8, _i64),
     "mf_conv3d_bf16_fwd_ws": ([_p, _p, _p, _p, _p, _i64] + [ctypes.c_int32] * 11 + [_p], _i),
+    "mf_conv2d_split_pack": ([_p] + [ctypes.c_int32] * 3 + [_p, _p], _i),
+    "mf_conv2d_split_workspace_bytes": ([ctypes.c_int32] * 8, _i64),
+    "mf_conv2d_split_fwd": ([_p, _p, _p, _p, ctypes.c_int32, _p, ctypes.c_int32, _p, ctypes.c_int32, _p, ctypes.c_int32,
+                             ctypes.c_int32, _p, _i64] + [ctypes.c_int32] * 8 + [_p], _i),
     "mf_conv3d_k3_narrow_bf16_pack_elems": ([ctypes.c_int32], _i64),
     "mf_conv3d_k3_narrow_bf16_pack": ([_p] + [ctypes.c_int32] * 5 + [_p, _p], _i),
     "mf_conv3d_k3_narrow_bf16": ([_p, _p, _p, _p] + [ctypes.c_int32] * 6 + [_p], _i),
@@ -151,6 +155,8 @@ _SIGNATURES = {
     "mf_interpolate_voxel_grid_cl_bf16_fwd": ([_p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _i64, _p], _i),
     "mf_interpolate_voxel_grid_cl_bf16_bwd": ([_p, _i64, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _i, _p], _i),
     "mf_upsample_bilinear_cl_fwd": ([_p, _p] + [ctypes.c_int32] * 7 + [_p], _i),
+    "mf_upsample_bilinear_cl_split_fwd": ([_p, _p] + [ctypes.c_int32] * 8 + [_p], _i),
+    "mf_split_bf16": ([_p, _i64, _i64, _i64, _i64] + [ctypes.c_int32] * 4 + [_p, ctypes.c_int32, ctypes.c_int32, _p], _i),
     "mf_upsample_bilinear_cl_bwd": ([_p, _p] + [ctypes.c_int32] * 7 + [_p], _i),
     "mf_upsample_bilinear_cf_fwd": ([_p, _p, _i64] + [ctypes.c_int32] * 5 + [_p], _i),
     "mf_upsample_bilinear_cf_bwd": ([_p, _p, _i64] + [ctypes.c_int32] * 5 + [_p], _i),

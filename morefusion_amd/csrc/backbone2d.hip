@@ -74,6 +74,63 @@ __global__ __launch_bounds__(256) void k_up_fwd(const void *__restrict__ x, void
   store8<BF16>(y, pix * C + 8 * c8, o);
 }
 
+// hi / lo of eight fp32 values -> y[idx ..] and y[idx + los ..] (the split-bf16 form of csrc/gemm_bf16.hip
+// mf_conv2d_split_fwd: hi = bf16(v), lo = bf16(v - hi), round to nearest even)
+__device__ __forceinline__ void store8_split(uint16_t *y, int64_t idx, int64_t los, const float v[8]) {
+  uint32_t h[8], l[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    h[k] = mf::bf16_bits(v[k]);
+    l[k] = mf::bf16_bits(v[k] - mf::bf16_lo(h[k]));
+  }
+  *reinterpret_cast<uint4 *>(y + idx) = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
+  *reinterpret_cast<uint4 *>(y + idx + los) =
+      make_uint4(l[0] | l[1] << 16, l[2] | l[3] << 16, l[4] | l[5] << 16, l[6] | l[7] << 16);
+}
+
+// k_up_fwd<false> with a split output: the resize of fp32 x [B][H][W][C] is taken in fp32 (same arithmetic), then
+// split into y [B][Ho][Wo] rows of pitch ldy: hi at channel c, lo at channel los + c.
+__global__ __launch_bounds__(256) void k_up_fwd_split(const float *__restrict__ x, uint16_t *__restrict__ y, int B, int H,
+                                                      int W, int Ho, int Wo, int C8, int ldy, int los) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t total = (int64_t)B * Ho * Wo * C8;
+  if (i >= total) return;
+  const int c8 = (int)(i % C8);
+  const int64_t pix = i / C8;
+  const int ox = (int)(pix % Wo), oy = (int)((pix / Wo) % Ho), b = (int)(pix / ((int64_t)Wo * Ho));
+  const float sy = up_scale(H, Ho) * (float)oy, sx = up_scale(W, Wo) * (float)ox;
+  const int y0 = (int)sy, x0 = (int)sx;
+  const int yp = y0 < H - 1 ? 1 : 0, xp = x0 < W - 1 ? 1 : 0;
+  const float h1 = sy - (float)y0, h0 = 1.0f - h1, w1 = sx - (float)x0, w0 = 1.0f - w1;
+  const int C = 8 * C8;
+  const int64_t base = (((int64_t)b * H + y0) * W + x0) * C + 8 * c8;
+  float a00[8], a01[8], a10[8], a11[8], o[8];
+  load8<false>(x, base, a00);
+  load8<false>(x, base + (int64_t)xp * C, a01);
+  load8<false>(x, base + (int64_t)yp * W * C, a10);
+  load8<false>(x, base + ((int64_t)yp * W + xp) * C, a11);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) o[k] = h0 * (w0 * a00[k] + w1 * a01[k]) + h1 * (w0 * a10[k] + w1 * a11[k]);
+  store8_split(y, pix * ldy + 8 * c8, los, o);
+}
+
+// x [B][C][H][W] fp32 at any element strides (channels-first or channels-last) -> the split form y [B][H][W] rows of
+// pitch ldy: hi at channel c, lo at channel los + c.  A lane takes one pixel x 8 channels.
+__global__ __launch_bounds__(256) void k_split_bf16(const float *__restrict__ x, int64_t sb, int64_t sc, int64_t sh,
+                                                    int64_t sw, int B, int C8, int H, int W, uint16_t *__restrict__ y,
+                                                    int ldy, int los) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * H * W * C8) return;
+  const int c8 = (int)(i % C8);
+  const int64_t pix = i / C8;
+  const int px = (int)(pix % W), py = (int)((pix / W) % H), b = (int)(pix / ((int64_t)W * H));
+  const float *src = x + b * sb + py * sh + px * sw + 8 * c8 * sc;
+  float v[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = src[k * sc];
+  store8_split(y, pix * ldy + 8 * c8, los, v);
+}
+
 // gx [B][H][W][C] = sum over the output pixels whose footprint contains (iy, ix), increasing (oy, ox)
 template <bool BF16>
 __global__ __launch_bounds__(256) void k_up_bwd(const void *__restrict__ gy, void *__restrict__ gx, int B, int H, int W,
@@ -450,6 +507,36 @@ extern "C" int mf_upsample_bilinear_cl_fwd(const void *x, void *y, int32_t B, in
   if (bf16) hipLaunchKernelGGL(k_up_fwd<true>, dim3(nb), dim3(256), 0, stream, x, y, B, H, W, Ho, Wo, C / 8);
   else hipLaunchKernelGGL(k_up_fwd<false>, dim3(nb), dim3(256), 0, stream, x, y, B, H, W, Ho, Wo, C / 8);
   return mf::check_launch("mf_upsample_bilinear_cl_fwd");
+}
+
+/* The resize of fp32 x [B, H, W, C] (channels-last, dense) split into y [B, Ho, Wo] rows of pitch ldy: hi(v) at
+ * channel c, lo(v) at channel los + c (the split-bf16 operand of mf_conv2d_split_fwd; y may be a channel block of a
+ * wider map).  C, ldy, los % 8 == 0, 16-byte aligned. */
+extern "C" int mf_upsample_bilinear_cl_split_fwd(const float *x, void *y, int32_t B, int32_t H, int32_t W, int32_t Ho,
+                                                 int32_t Wo, int32_t C, int32_t ldy, int32_t los, mfStream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if ((int64_t)B * Ho * Wo * C == 0) return 0;
+  if (C % 8 || ldy % 8 || los % 8 || los < C || ldy < los + C || H < 1 || W < 1 ||
+      (((uintptr_t)x | (uintptr_t)y) & 15))
+    return bad2d("upsample_bilinear_cl_split: C, ldy, los % 8 == 0, los >= C, ldy >= los + C, aligned");
+  const int64_t total = (int64_t)B * Ho * Wo * (C / 8);
+  hipLaunchKernelGGL(k_up_fwd_split, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x, (uint16_t *)y, B, H,
+                     W, Ho, Wo, C / 8, ldy, los);
+  return mf::check_launch("mf_upsample_bilinear_cl_split_fwd");
+}
+
+/* fp32 x [B, C, H, W] at element strides (sb, sc, sh, sw) -> its split form y [B, H, W] rows of pitch ldy: hi at
+ * channel c, lo at channel los + c.  C, ldy, los % 8 == 0, y 16-byte aligned. */
+extern "C" int mf_split_bf16(const float *x, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int32_t B, int32_t C,
+                             int32_t H, int32_t W, void *y, int32_t ldy, int32_t los, mfStream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if ((int64_t)B * C * H * W == 0) return 0;
+  if (C % 8 || ldy % 8 || los % 8 || los < C || ldy < los + C || ((uintptr_t)y & 15))
+    return bad2d("split_bf16: C, ldy, los % 8 == 0, los >= C, ldy >= los + C, aligned output");
+  const int64_t total = (int64_t)B * H * W * (C / 8);
+  hipLaunchKernelGGL(k_split_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x, sb, sc, sh, sw, B,
+                     C / 8, H, W, (uint16_t *)y, ldy, los);
+  return mf::check_launch("mf_split_bf16");
 }
 
 extern "C" int mf_upsample_bilinear_cl_bwd(const void *gy, void *gx, int32_t B, int32_t H, int32_t W, int32_t Ho,

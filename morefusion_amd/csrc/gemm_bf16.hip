@@ -42,7 +42,7 @@ template <int MI> constexpr int nt_lds() {
   return 2 * nt_buf_bytes<MI>() > 64 * MI * (kBN + 4) * 4 ? 2 * nt_buf_bytes<MI>() : 64 * MI * (kBN + 4) * 4;
 }
 
-enum { kRows = 0, kConvFwd = 1, kConvDgrad = 2 };
+enum { kRows = 0, kConvFwd = 1, kConvDgrad = 2, kConv2Fwd = 3 };
 
 struct NtArgs {
   const uint16_t *A;   // bf16 operand (rows / channels-last grid / channels-last output gradient)
@@ -63,9 +63,54 @@ struct NtArgs {
   // sums (no bias / ReLU) to slab + s * M * N (row pitch N), k_splitk_finish adds them in order
   int S;
   float *slab;
+  // 2-D split-bf16 convolution (kConv2Fwd, mf_conv2d_split_fwd): the input is [B][D][D][xc] bf16 with xc = 2 C (hi
+  // plane, then lo plane); Cin = 3 C is the K length of one tap, whose source channel is k mod xc (segments
+  // [hi | lo | hi] against the packed weights [w_hi | w_hi | w_lo]).  Epilogue (conv2_store8):
+  //   v = act(acc + bias[n] + res[m][n])   act: 0 none, 1 ReLU, 2 PReLU with the single slope *slope
+  //   out32[m][n] = v (pitch ldo32), outs[m][n] = bf16(v), outs[m][los + n] = bf16(v - bf16(v)) (pitch ldos)
+  int xc, act, ldr, ldo32, ldos, los;
+  const float *res, *slope;
+  float *out32;
+  uint16_t *outs;
   int dbg;  // k_gemm_nt_bf16_pp ablations (MF_PP_DBG; timing experiments only, results are wrong): see launch_nt
 };
 
+// The kConv2Fwd epilogue of eight columns n .. n + 7 of output row m (N % 8 == 0; every pitch a multiple of 8 and every
+// pointer 16-byte aligned: checked by mf_conv2d_split_fwd).  hi = bf16(v) and lo = bf16(v - hi), both round-to-nearest-
+// even; v - hi is exact in fp32.
+__device__ __forceinline__ void conv2_store8(const NtArgs &a, int64_t m, int n, float *v) {
+  if (a.bias) {
+    const float4 b0 = *reinterpret_cast<const float4 *>(a.bias + n), b1 = *reinterpret_cast<const float4 *>(a.bias + n + 4);
+    v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w; v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
+  }
+  if (a.res) {
+    const float *r = a.res + m * a.ldr + n;
+    const float4 r0 = *reinterpret_cast<const float4 *>(r), r1 = *reinterpret_cast<const float4 *>(r + 4);
+    v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w; v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w;
+  }
+  if (a.act) {
+    const float s = a.act == 2 ? *a.slope : 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = v[j] > 0.0f ? v[j] : s * v[j];
+  }
+  if (a.out32) {
+    float4 *o = reinterpret_cast<float4 *>(a.out32 + m * a.ldo32 + n);
+    o[0] = make_float4(v[0], v[1], v[2], v[3]);
+    o[1] = make_float4(v[4], v[5], v[6], v[7]);
+  }
+  if (a.outs) {
+    uint32_t h[8], l[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      h[j] = mf::bf16_bits(v[j]);
+      l[j] = mf::bf16_bits(v[j] - mf::bf16_lo(h[j]));
+    }
+    uint16_t *o = a.outs + m * a.ldos + n;
+    *reinterpret_cast<uint4 *>(o) = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
+    *reinterpret_cast<uint4 *>(o + a.los) =
+        make_uint4(l[0] | l[1] << 16, l[2] | l[3] << 16, l[4] | l[5] << 16, l[6] | l[7] << 16);
+  }
+}
 
 template <int MODE, int MI>
 __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
@@ -112,6 +157,15 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
     int mk = row_ok ? 1 << 12 : 0;
     if (MODE == kRows) {
       base[i] = mm * a.lda;
+    } else if (MODE == kConv2Fwd) {  // row m = (b, oy, ox); bits ky | 4 + kx = tap row / column inside the map
+      const int b = mm >> (2 * dol), o = mm & ((1 << (2 * dol)) - 1);
+      const int y0 = a.stride * (o >> dol) - a.pad, x0 = a.stride * (o & (Do - 1)) - a.pad;
+      base[i] = ((b * a.D + y0) * a.D + x0) * a.xc;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {  // (k >= ks: never asked for)
+        mk |= ((unsigned)(y0 + a.dil * k) < (unsigned)a.D ? 1 : 0) << k;
+        mk |= ((unsigned)(x0 + a.dil * k) < (unsigned)a.D ? 1 : 0) << (4 + k);
+      }
     } else if (MODE == kConvFwd) {
       const int b = mm >> (3 * dol), o = mm & ((1 << (3 * dol)) - 1);
       const int ox = o >> (2 * dol), oy = (o >> dol) & (Do - 1), oz = o & (Do - 1);
@@ -171,6 +225,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
     tc = kg - tap * a.Cin;
     const int kxy = tap / a.ks;
     tz = tap - kxy * a.ks; tx = kxy / a.ks; ty = kxy - tx * a.ks;
+  } else if (MODE == kConv2Fwd) {  // tap (ky, kx) = (tx, ty), position tc in the tap's 3 C
+    const int tap = kg / a.Cin;
+    tc = kg - tap * a.Cin;
+    tx = tap / a.ks; ty = tap - tx * a.ks;
   } else if (MODE == kConvDgrad) {
     tx = kg / a.Cout;
     tc = kg - tx * a.Cout;
@@ -192,6 +250,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
     if (MODE == kConvFwd) {                                                                           \
       off_ = ((tx * a.D + ty) * a.D + tz) * a.dil * a.Cin + tc;                                       \
       bits_ = tx < a.ks ? (1 << tx) | (16 << ty) | (256 << tz) | (1 << 12) : 1 << 13;                 \
+    } else if (MODE == kConv2Fwd) {                                                                   \
+      off_ = (tx * a.D + ty) * a.dil * a.xc + (tc >= a.xc ? tc - a.xc : tc);                          \
+      bits_ = tx < a.ks ? (1 << tx) | (16 << ty) | (1 << 12) : 1 << 13;                               \
     } else if (MODE == kConvDgrad) {                                                                  \
       const int sx = tx & 1, sy = (tx >> 1) & 1, sz = tx >> 2;                                        \
       off_ = tc - ((sx * Do + sy) * Do + sz) * a.Cout;                                                \
@@ -207,6 +268,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
       while (tc >= a.Cin) {                                                                           \
         tc -= a.Cin;                                                                                  \
         if (++tz == a.ks) { tz = 0; if (++ty == a.ks) { ty = 0; ++tx; } }                             \
+      }                                                                                               \
+    } else if (MODE == kConv2Fwd) {                                                                   \
+      tc += kBK;                                                                                      \
+      while (tc >= a.Cin) {                                                                           \
+        tc -= a.Cin;                                                                                  \
+        if (++ty == a.ks) { ty = 0; ++tx; }                                                           \
       }                                                                                               \
     } else if (MODE == kConvDgrad) {                                                                  \
       tc += kBK;                                                                                      \
@@ -309,7 +376,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
   // epilogue through LDS (the loop ended on a barrier: the operand buffers are free)
   constexpr int kEp = kBN + 4;
   float *s_out = reinterpret_cast<float *>(s_raw);  // [kBM][kEp]
-  const float *bias = a.bias ? a.bias + grp * a.b_gs : nullptr;
+  const float *bias = a.bias && MODE != kConv2Fwd ? a.bias + grp * a.b_gs : nullptr;  // (conv2: conv2_store8)
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -320,7 +387,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
       for (int e = 0; e < 16; ++e) {
         const int ml = wm * 32 * MI + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * lhalf;
         float v = acc[mi][ni][e] + bn;
-        if (a.relu) v = v > 0.0f ? v : 0.0f;
+        if (a.relu && MODE != kConv2Fwd) v = v > 0.0f ? v : 0.0f;
         s_out[ml * kEp + nl] = v;
       }
     }
@@ -339,6 +406,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
     const float4 v0 = *reinterpret_cast<const float4 *>(s_out + ml * kEp + 8 * c8);
     const float4 v1 = *reinterpret_cast<const float4 *>(s_out + ml * kEp + 8 * c8 + 4);
     float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+    if (MODE == kConv2Fwd) {
+      conv2_store8(a, m, n, v);
+      continue;
+    }
     const int nv = a.N - n < 8 ? a.N - n : 8;
     if (a.out_f32) {
       float *o = reinterpret_cast<float *>(a.out) + grp * a.o_gs + orow * a.ldo + n;
@@ -451,6 +522,15 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_bf16_pp(NtArgs a) {
     int mk = row_ok ? 1 << 12 : 0;
     if (MODE == kRows) {
       base[i] = mm * a.lda;
+    } else if (MODE == kConv2Fwd) {  // row m = (b, oy, ox); bits ky | 4 + kx = tap row / column inside the map
+      const int b = mm >> (2 * dol), o = mm & ((1 << (2 * dol)) - 1);
+      const int y0 = a.stride * (o >> dol) - a.pad, x0 = a.stride * (o & (Do - 1)) - a.pad;
+      base[i] = ((b * a.D + y0) * a.D + x0) * a.xc;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {  // (k >= ks: never asked for)
+        mk |= ((unsigned)(y0 + a.dil * k) < (unsigned)a.D ? 1 : 0) << k;
+        mk |= ((unsigned)(x0 + a.dil * k) < (unsigned)a.D ? 1 : 0) << (4 + k);
+      }
     } else if (MODE == kConvFwd) {
       const int b = mm >> (3 * dol), o = mm & ((1 << (3 * dol)) - 1);
       const int ox = o >> (2 * dol), oy = (o >> dol) & (Do - 1), oz = o & (Do - 1);
@@ -499,6 +579,10 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_bf16_pp(NtArgs a) {
     tc = kg - tap * a.Cin;
     const int kxy = tap / a.ks;
     tz = tap - kxy * a.ks; tx = kxy / a.ks; ty = kxy - tx * a.ks;
+  } else if (MODE == kConv2Fwd) {  // tap (ky, kx) = (tx, ty), position tc in the tap's 3 C
+    const int tap = kg / a.Cin;
+    tc = kg - tap * a.Cin;
+    tx = tap / a.ks; ty = tap - tx * a.ks;
   } else if (MODE == kConvDgrad) {
     tx = kg / a.Cout;
     tc = kg - tx * a.Cout;
@@ -514,6 +598,9 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_bf16_pp(NtArgs a) {
     if (MODE == kConvFwd) {                                                                           \
       off_ = ((tx * a.D + ty) * a.D + tz) * a.dil * a.Cin + tc;                                       \
       bits_ = tx < a.ks ? (1 << tx) | (16 << ty) | (256 << tz) | (1 << 12) : 1 << 13;                 \
+    } else if (MODE == kConv2Fwd) {                                                                   \
+      off_ = (tx * a.D + ty) * a.dil * a.xc + (tc >= a.xc ? tc - a.xc : tc);                          \
+      bits_ = tx < a.ks ? (1 << tx) | (16 << ty) | (1 << 12) : 1 << 13;                               \
     } else if (MODE == kConvDgrad) {                                                                  \
       const int sx = tx & 1, sy = (tx >> 1) & 1, sz = tx >> 2;                                        \
       off_ = tc - ((sx * Do + sy) * Do + sz) * a.Cout;                                                \
@@ -530,6 +617,12 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_bf16_pp(NtArgs a) {
         while (tc >= a.Cin) {                                                                         \
           tc -= a.Cin;                                                                                \
           if (++tz == a.ks) { tz = 0; if (++ty == a.ks) { ty = 0; ++tx; } }                           \
+        }                                                                                             \
+      } else if (MODE == kConv2Fwd) {                                                                 \
+        tc += kBK;                                                                                    \
+        while (tc >= a.Cin) {                                                                         \
+          tc -= a.Cin;                                                                                \
+          if (++ty == a.ks) { ty = 0; ++tx; }                                                         \
         }                                                                                             \
       } else if (MODE == kConvDgrad) {                                                                \
         tc += kBK;                                                                                    \
@@ -640,8 +733,8 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_bf16_pp(NtArgs a) {
   // epilogue through LDS in four passes of 64 rows (64 x 260 floats)
   constexpr int kEp = kBNb + 4;
   float *s_out = reinterpret_cast<float *>(s_raw);  // [64][kEp]
-  const float *bias = a.bias && a.S == 1 ? a.bias + grp * a.b_gs : nullptr;
-  const bool relu = a.relu && a.S == 1, out_f32 = a.out_f32 || a.S > 1;
+  const float *bias = a.bias && a.S == 1 && MODE != kConv2Fwd ? a.bias + grp * a.b_gs : nullptr;  // (conv2: conv2_store8)
+  const bool relu = a.relu && a.S == 1 && MODE != kConv2Fwd, out_f32 = a.out_f32 || a.S > 1;
   const int ldo = a.S > 1 ? a.N : a.ldo;
   void *const outp = a.S > 1 ? (void *)(a.slab + (int64_t)split * a.M * a.N) : a.out;
 #pragma unroll
@@ -678,6 +771,10 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_bf16_pp(NtArgs a) {
       const float4 v0 = *reinterpret_cast<const float4 *>(s_out + ml * kEp + 8 * c8);
       const float4 v1 = *reinterpret_cast<const float4 *>(s_out + ml * kEp + 8 * c8 + 4);
       float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+      if (MODE == kConv2Fwd && a.S == 1) {
+        conv2_store8(a, m, n, v);
+        continue;
+      }
       const int nv = a.N - n < 8 ? a.N - n : 8;
       if (out_f32) {
         float *o = reinterpret_cast<float *>(outp) + grp * a.o_gs + orow * ldo + n;
@@ -1386,6 +1483,41 @@ __global__ __launch_bounds__(256) void k_splitk_finish(const float *__restrict__
   }
 }
 
+// The same sum for a split-K launch of the 2-D split-bf16 convolution, through its epilogue (conv2_store8).
+__global__ __launch_bounds__(256) void k_splitk_finish_conv2(NtArgs a) {
+  const int n8 = a.N >> 3;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)a.M * n8) return;
+  const int64_t m = i / n8;
+  const int n = (int)(i - m * n8) * 8;
+  const float4 *src = reinterpret_cast<const float4 *>(a.slab + m * a.N + n);
+  float4 a0 = src[0], a1 = src[1];
+  for (int s = 1; s < a.S; ++s) {
+    const float4 *p = reinterpret_cast<const float4 *>(a.slab + (int64_t)s * a.M * a.N + m * a.N + n);
+    const float4 b0 = p[0], b1 = p[1];
+    a0.x += b0.x; a0.y += b0.y; a0.z += b0.z; a0.w += b0.w;
+    a1.x += b1.x; a1.y += b1.y; a1.z += b1.z; a1.w += b1.w;
+  }
+  float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+  conv2_store8(a, m, n, v);
+}
+
+// W [Cout][Cin][ks][ks] fp32 (framework layout) -> wp bf16 [Cout][tap][3 Cin] = [w_hi | w_hi | w_lo] per tap, the
+// operand of the 2-D split-bf16 convolution (w_hi = bf16(w), w_lo = bf16(w - w_hi)).
+__global__ __launch_bounds__(256) void k_conv2_pack_split(const float *__restrict__ W, int Cout, int Cin, int taps,
+                                                          uint16_t *__restrict__ wp) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int K3 = 3 * Cin;
+  if (i >= (int64_t)Cout * taps * K3) return;
+  const int j = (int)(i % K3);
+  const int64_t r = i / K3;
+  const int tap = (int)(r % taps), n = (int)(r / taps);
+  const int seg = j / Cin, c = j - seg * Cin;
+  const float w = W[((int64_t)n * Cin + c) * taps + tap];
+  const uint32_t hb = mf::bf16_bits(w);
+  wp[i] = (uint16_t)(seg < 2 ? hb : mf::bf16_bits(w - mf::bf16_lo(hb)));
+}
+
 // ---- 3 x 3 x 3 convolutions between NARROW layers (round 6): the occupancy branch ----------------------------------
 // conv1_occ (1 -> 8, fed as 8 channels), conv2_occ (8 -> 16, dilation 2) and conv2_occ's data gradient (16 -> 8)
 // (model.py:69-72,120-124) went through k_gemm_nt_bf16<conv forward>: 8 or 16 valid columns of a 128-column tile,
@@ -1513,7 +1645,10 @@ int launch_nt(const NtArgs &a, hipStream_t stream) {
     if (b.S < 1) b.S = 1;
     if (int e = mf::allow_big_lds((const void *)k_gemm_nt_bf16_pp<MODE>, nt_pp_lds())) return e;
     hipLaunchKernelGGL((k_gemm_nt_bf16_pp<MODE>), dim3((unsigned)(big * b.S)), dim3(512), nt_pp_lds(), stream, b);
-    if (b.S > 1)
+    if (b.S > 1 && MODE == kConv2Fwd)
+      hipLaunchKernelGGL(k_splitk_finish_conv2, dim3((unsigned)(((int64_t)a.M * (a.N / 8) + 255) / 256)), dim3(256), 0,
+                         stream, b);
+    else if (b.S > 1)
       hipLaunchKernelGGL(k_splitk_finish, dim3((unsigned)(((int64_t)a.M * (a.N / 8) + 255) / 256)), dim3(256), 0,
                          stream, (const float *)b.slab, a.bias, a.out, (int64_t)a.M, a.N, b.S, a.ldo, a.relu,
                          a.out_f32);
@@ -1969,3 +2104,78 @@ extern "C" int mf_conv3d_k4s2_bf16_wgrad(const void *dy, const void *x, float *d
 /* Tile height (64 / 128 / 256 rows) of the NT engine's most recent launch in this process: lets tests and the
  * timing tools see which form of the engine a problem was given to (launch_nt's choice, MF_NT_BIG). */
 extern "C" int mf_gemm_bf16_last_tile(void) { return g_nt_last_tile; }
+
+/* 2-D convolutions of the inference backbone as split-bf16 GEMMs.  An fp32 value x is carried as
+ * hi = bf16(x) and lo = bf16(x - hi); a product x w is taken as hi hi + lo w_hi + hi w_lo (three exact bf16 products,
+ * fp32 accumulation): relative error per product <= ~3 * 2^-18, the dropped lo lo term included.
+ *   xs   bf16 [B][D][D][2 Cin]  (channels-last map: the Cin hi channels, then the Cin lo channels)
+ *   wp   bf16 [Cout][ks^2][3 Cin] from mf_conv2d_split_pack
+ *   out  row m = (b, oy, ox) of the Do x Do output map, Do = (D + 2 pad - dil (ks - 1) - 1) / stride + 1 a power of two:
+ *        v = act(conv + bias + res[m])  (act 0 none, 1 ReLU, 2 PReLU with the single slope *slope: read on the device)
+ *        out32[m * ldo32 + n] = v  and / or  outs[m * ldos + n] = hi(v), outs[m * ldos + los + n] = lo(v)
+ *   ws   mf_conv2d_split_workspace_bytes(...) bytes of fp32 split-K slabs (0: none needed, ws may be null) */
+namespace {
+int conv2_geom(int32_t B, int32_t Cin, int32_t Cout, int32_t D, int32_t ks, int32_t stride, int32_t pad, int32_t dil,
+               Geom *g) {
+  const int span = dil * (ks - 1) + 1;
+  if ((ks != 1 && ks != 3) || (stride != 1 && stride != 2) || dil < 1 || dil > 4 || pad < 0 || D + 2 * pad < span)
+    return bad("conv2d_split: kernel 1 or 3, stride 1 or 2, dilation 1 .. 4");
+  g->Do = (D + 2 * pad - span) / stride + 1;
+  g->olog = ilog2_exact(g->Do);
+  g->taps = ks * ks;
+  if (g->olog < 0 || Cin % 8 || Cout % 8 || (int64_t)B * D * D * 2 * Cin >= kMaxBf16Elems ||
+      (int64_t)B * g->Do * g->Do >= (1ll << 31) || (int64_t)Cout * g->taps * 3 * Cin >= kMaxBf16Elems)
+    return bad("conv2d_split: output side a power of two, Cin % 8 == 0, Cout % 8 == 0, operands < 2^30 elements");
+  return 0;
+}
+}  // namespace
+
+extern "C" int mf_conv2d_split_pack(const float *W, int32_t Cout, int32_t Cin, int32_t ks, void *wp, mfStream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (Cout <= 0 || Cin <= 0) return 0;
+  if ((ks != 1 && ks != 3) || ((uintptr_t)wp & 15)) return bad("conv2d_split_pack: kernel 1 or 3, aligned output");
+  const int64_t n = (int64_t)Cout * ks * ks * 3 * Cin;
+  hipLaunchKernelGGL(k_conv2_pack_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, W, Cout, Cin, ks * ks,
+                     (uint16_t *)wp);
+  return mf::check_launch("mf_conv2d_split_pack");
+}
+
+extern "C" int64_t mf_conv2d_split_workspace_bytes(int32_t B, int32_t Cin, int32_t Cout, int32_t D, int32_t ks,
+                                                   int32_t stride, int32_t pad, int32_t dil) {
+  Geom g;
+  if (B <= 0 || conv2_geom(B, Cin, Cout, D, ks, stride, pad, dil, &g)) return 0;
+  const int64_t M = (int64_t)B * g.Do * g.Do;
+  const int S = nt_splitk(M, Cout, g.taps * 3 * Cin);
+  return S > 1 ? (int64_t)S * M * Cout * 4 : 0;
+}
+
+extern "C" int mf_conv2d_split_fwd(const void *xs, const void *wp, const float *bias, const float *res, int32_t ldr,
+                                   const float *slope, int32_t act, float *out32, int32_t ldo32, void *outs, int32_t ldos,
+                                   int32_t los, void *ws, int64_t ws_bytes, int32_t B, int32_t Cin, int32_t Cout,
+                                   int32_t D, int32_t ks, int32_t stride, int32_t pad, int32_t dil, mfStream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B <= 0) return 0;
+  Geom g;
+  if (int e = conv2_geom(B, Cin, Cout, D, ks, stride, pad, dil, &g)) return e;
+  if ((!out32 && !outs) || act < 0 || act > 2 || (act == 2 && !slope))
+    return bad("conv2d_split_fwd: at least one output; act 0 / 1 / 2 (PReLU needs its slope)");
+  if ((out32 && (ldo32 < Cout || ldo32 % 8)) || (outs && (ldos < Cout || ldos % 8 || los < Cout || los % 8 ||
+                                                           ldos < los + Cout)) || (res && (ldr < Cout || ldr % 8)))
+    return bad("conv2d_split_fwd: output / residual pitches >= Cout and multiples of 8; lo plane inside the row");
+  if (((uintptr_t)xs | (uintptr_t)wp | (uintptr_t)bias | (uintptr_t)res | (uintptr_t)out32 | (uintptr_t)outs |
+       (uintptr_t)ws) & 15)
+    return bad("conv2d_split_fwd: 16-byte aligned operands");
+  const int64_t M = (int64_t)B * g.Do * g.Do;
+  int S = nt_splitk(M, Cout, g.taps * 3 * Cin);
+  if (S > 1 && (!ws || ws_bytes < (int64_t)S * M * Cout * 4)) S = 1;
+  NtArgs a = {};
+  a.A = (const uint16_t *)xs; a.W = (const uint16_t *)wp; a.bias = bias;
+  a.M = (int)M; a.N = Cout; a.K = g.taps * 3 * Cin; a.ldw = g.taps * 3 * Cin; a.groups = 1;
+  a.B = B; a.D = D; a.Do = g.Do; a.olog = g.olog; a.Cin = 3 * Cin; a.Cout = Cout;
+  a.ks = ks; a.stride = stride; a.pad = pad; a.dil = dil;
+  a.xc = 2 * Cin; a.act = act; a.ldr = ldr; a.ldo32 = ldo32; a.ldos = ldos; a.los = los;
+  a.res = res; a.slope = slope; a.out32 = out32; a.outs = (uint16_t *)outs;
+  a.S = S; a.slab = S > 1 ? (float *)ws : nullptr;
+  if (int e = launch_nt<kConv2Fwd>(a, stream)) return e;
+  return mf::check_launch("mf_conv2d_split_fwd");
+}

@@ -1,9 +1,20 @@
 """2-D backbone of the pose network: DenseFusion-style ResNet18 + PSPNet decoder.
 
 Restates morefusion/models/dense_fusion/resnet.py:9-136 and pspnet.py:10-82 with stock
-``torch.nn`` layers (dense 2-D convolutions -> MIOpen; not hand-written).
-No BatchNorm anywhere (the reference has none); ``F.resize_images`` == bilinear with
-align_corners=True; PReLU has one shared slope initialised to 0.25.
+``torch.nn`` layers.  No BatchNorm anywhere (the reference has none); ``F.resize_images`` ==
+bilinear with align_corners=True; PReLU has one shared slope initialised to 0.25.
+
+Inference in fp32 (CUDA, eval mode, no grad, no autocast) runs the large convolutions -- res4,
+res5, psp.bottleneck, up1.conv and up2.conv, 98 % of the network's FLOPs -- as split-bf16 GEMMs
+on the MFMA engine of csrc/gemm_bf16.hip (mf_conv2d_split_fwd): every fp32 value
+x is carried as hi = bf16(x), lo = bf16(x - hi) and a product x w as hi w_hi + lo w_hi + hi w_lo,
+accumulated in fp32.  Per product that differs from x w by at most ~3 * 2^-18 relative (the
+split leaves <= 2^-18 |x|, the dropped lo lo term <= 2^-18 |x w|): ~40x tighter than TF32, not
+bit-equal to MIOpen.  Maps stay in split form between the convolutions; bias, residual, ReLU /
+PReLU and both output forms are the GEMM's epilogue.  Everything else (conv1, res2, res3, the
+pooled-branch 1x1 convolutions, training, autocast) stays on MIOpen, and so do res4 / res5 / up2
+below SPLIT_MIN_BATCH objects (the dispatch table).  ``split_bf16 = False``
+on ``ResNet18`` / ``PSPNetExtractor`` switches the path off (A/B runs).
 """
 
 import os
@@ -39,8 +50,39 @@ class ResBlock(nn.Sequential):
         super().__init__(*blocks)
 
 
+# Dispatch of the split-bf16 path: the smallest batch at which a layer group runs it instead of MIOpen, from per-layer
+# times at 1 and 8 objects (tools/time_conv2d_split.py).  At one object res4 / res5 / up2 have too few
+# output tiles for the GEMM (32-64 workgroups on 256 CUs) and MIOpen is faster; up1 is 2x faster split at any batch.
+SPLIT_MIN_BATCH = {"res4_res5": 4, "psp_up1": 1, "up2": 4}
+
+
+def _split_path(module, x, group):
+    """The split-bf16 path's conditions: fp32 inference on the GPU (eval mode, no grad, no autocast), batch per the
+    dispatch table, and the geometry the GEMM's address mode takes -- a square map [B,C,D,D] whose side D is a power of
+    two (every in-scope layer keeps the side or doubles it).  Any other map stays on MIOpen."""
+    D = x.shape[2]
+    return (module.split_bf16 and x.is_cuda and x.dtype == torch.float32 and not module.training
+            and not torch.is_grad_enabled() and not torch.is_autocast_enabled()
+            and x.shape[0] >= SPLIT_MIN_BATCH[group] and x.shape[3] == D and D > 0 and D & (D - 1) == 0)
+
+
+def _block_split(blk, xs, x32, need32=True, needs=True):
+    """``BasicBlock.forward`` on split maps: xs [B,D,D,2 Cin] (and x32, its fp32 form, for an identity shortcut) ->
+    (split, fp32) of relu(conv2(relu(conv1(x))) + residual); only the forms the caller reads are written (None for the
+    others)."""
+    if blk.residual_conv is not None:
+        r, _ = ops2d.conv_split(xs, blk.residual_conv)
+    else:
+        r = x32
+    _, t = ops2d.conv_split(xs, blk.conv1, act=1, out32=False, outs=True)
+    y32, ys = ops2d.conv_split(t, blk.conv2, res=r, act=1, out32=need32, outs=needs)
+    return ys, y32
+
+
 class ResNet18(nn.Module):
     """[B,3,H,W] uint8-range float -> [B,512,H/8,W/8] (dense_fusion/resnet.py:9-58)."""
+
+    split_bf16 = True  # res4 / res5 as split-bf16 GEMMs in fp32 inference (module docstring)
 
     mean_rgb = (0.485, 0.456, 0.406)
     std_rgb = (0.229, 0.224, 0.225)
@@ -59,7 +101,17 @@ class ResNet18(nn.Module):
         h = (x / 255.0 - self.mean) / self.std
         h = self.conv1(h)
         h = F.max_pool2d(h, 3, 2, 1)
-        return self.res5(self.res4(self.res3(self.res2(h))))
+        h = self.res3(self.res2(h))
+        if _split_path(self, h, "res4_res5"):
+            blocks = list(self.res4) + list(self.res5)
+            xs, x32 = ops2d.to_split(h), None
+            for i, blk in enumerate(blocks):
+                nxt = blocks[i + 1] if i + 1 < len(blocks) else None
+                # fp32 for the next block's identity shortcut and for the output; split form for the next block only
+                xs, x32 = _block_split(blk, xs, x32, need32=nxt is None or nxt.residual_conv is None,
+                                       needs=nxt is not None)
+            return x32.permute(0, 3, 1, 2)  # [B,512,h,w] in channels-last memory
+        return self.res5(self.res4(h))
 
 
 class _ConvBlock(nn.Module):
@@ -263,6 +315,7 @@ class PSPNetExtractor(nn.Module):
         self.conv1 = nn.Conv2d(64, 32, 1)
 
     bf16_tail_kernels = True  # the sampled tail under bf16 autocast on the hand-written kernels (_tail_rows_bf16)
+    split_bf16 = True  # psp.bottleneck, up1.conv, up2.conv as split-bf16 GEMMs in fp32 inference (module docstring)
 
     def __getstate__(self):  # the tail kernel's packed weights are a cache
         state = dict(self.__dict__)
@@ -319,9 +372,16 @@ class PSPNetExtractor(nn.Module):
         GEMM input): the taps' index arithmetic, the four gathers, the 3x3 convolution + PReLU, the 1x1
         convolution and the log-softmax of the torch formulation (~55 launches) fused.  Inference, fp32, CUDA."""
         from .. import _lib
-        h = self.psp(x)
-        h = self.up1(h)
-        u2 = self.up2(h)  # [B,64,H,W], H = W = 128; NCHW or channels-last strides, both read in place
+        if _split_path(self, x, "psp_up1") and self.up1.prelu.weight.numel() == 1:
+            h = self._psp_up1_split(x)  # fp32 [B, 2H, 2W, 256]
+            if _split_path(self, x, "up2") and self.up2.prelu.weight.numel() == 1:
+                us = ops2d.upsample_split(h, 2 * h.shape[1], 2 * h.shape[2])
+                u2, _ = ops2d.conv_split(us, self.up2.conv, act=2, slope=self.up2.prelu.weight.detach())
+                u2 = u2.permute(0, 3, 1, 2)
+            else:
+                u2 = self.up2(h.permute(0, 3, 1, 2))
+        else:
+            u2 = self.up2(self.up1(self.psp(x)))  # [B,64,H,W], H = W = 128; NCHW or channels-last strides, both read in place
         if u2.dtype != torch.float32:
             u2 = u2.float()
         B, C, H, W = u2.shape
@@ -345,6 +405,24 @@ class PSPNetExtractor(nn.Module):
             w1t.data_ptr(), self.conv1.bias.detach().float().data_ptr(), B, P, H, W, out.data_ptr(),
             _lib.stream_ptr()), "mf_psp_tail_fwd")
         return out
+
+    def _psp_up1_split(self, x):
+        """``up1(psp(x))`` with the bottleneck and up1's convolution on split maps: the four up-sampled branches and x
+        are written in split form straight into the concat map [B,H,W,2 * 5C] (hi channels of the concat, then its lo
+        channels), the bottleneck (+ bias + ReLU) gives fp32 for the resize, the resize writes split form again and
+        up1.conv (+ bias + PReLU) gives fp32 [B,2H,2W,256] (channels-last)."""
+        psp = self.psp
+        B, C, H, W = x.shape
+        Ct = C * (len(psp.sizes) + 1)
+        cat = torch.empty((B, H, W, 2 * Ct), dtype=torch.bfloat16, device=x.device)
+        for i, (pooled, conv) in enumerate(zip(psp._pooled(x), psp.convs)):
+            hb = conv(pooled).permute(0, 2, 3, 1).contiguous()
+            ops2d.upsample_split(hb, H, W, out=cat, c_off=i * C, los=Ct)
+        ops2d.to_split(x, out=cat, c_off=Ct - C, los=Ct)
+        b32, _ = ops2d.conv_split(cat, psp.bottleneck, act=1)
+        us = ops2d.upsample_split(b32, 2 * H, 2 * W)
+        h, _ = ops2d.conv_split(us, self.up1.conv, act=2, slope=self.up1.prelu.weight.detach())
+        return h
 
     @staticmethod
     def _tail_taps(pix, H, W):

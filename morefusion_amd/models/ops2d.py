@@ -199,3 +199,71 @@ def upsample_bilinear(x, size):
 def prelu(x, slope):
     """``F.prelu(x, slope)`` for a single slope."""
     return _PReLU.apply(_autocast_dtype(x), slope)
+
+
+# ---- split-bf16 convolutions (csrc/gemm_bf16.hip mf_conv2d_split_fwd): inference, fp32, channels-last ----------------
+# A map in split form is a bf16 tensor [B, H, W, 2C]: the C hi channels bf16(x), then the C lo channels bf16(x - hi).
+
+def split_pack(conv):
+    """``conv.weight`` [Cout, Cin, k, k] -> bf16 [Cout, k*k, 3 Cin] = [w_hi | w_hi | w_lo] per tap, cached on the module
+    by the parameter's address and in-place version (rebuilt, not cached, when first asked for under graph capture)."""
+    w = conv.weight
+    key = (w.data_ptr(), w._version)
+    hit = conv.__dict__.get("_split_pack")
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    Cout, Cin, k, _ = w.shape
+    wp = torch.empty((Cout, k * k, 3 * Cin), dtype=torch.bfloat16, device=w.device)
+    wf = w.detach().float().contiguous()
+    _lib.check(_lib.lib().mf_conv2d_split_pack(wf.data_ptr(), Cout, Cin, k, wp.data_ptr(), _lib.stream_ptr()),
+               "mf_conv2d_split_pack")
+    if not torch.cuda.is_current_stream_capturing():
+        conv.__dict__["_split_pack"] = (key, wp)
+    return wp
+
+
+def to_split(x, out=None, c_off=0, los=None):
+    """fp32 [B, C, H, W] (any strides) -> split form [B, H, W, 2C]; or into channels c_off .. of ``out`` [B, H, W, ldy]
+    (hi at c_off + c, lo at c_off + los + c)."""
+    B, C, H, W = x.shape
+    if out is None:
+        out, los = torch.empty((B, H, W, 2 * C), dtype=torch.bfloat16, device=x.device), C
+    _lib.check(_lib.lib().mf_split_bf16(x.data_ptr(), *x.stride(), B, C, H, W, out[..., c_off:].data_ptr(),
+                                        out.shape[3], los, _lib.stream_ptr()), "mf_split_bf16")
+    return out
+
+
+def upsample_split(x_cl, Ho, Wo, out=None, c_off=0, los=None):
+    """Bilinear resize (align_corners) of fp32 channels-last x [B, H, W, C], taken in fp32, -> split form [B, Ho, Wo, 2C]
+    (or into channels c_off .. of ``out`` as ``to_split``)."""
+    B, H, W, C = x_cl.shape
+    if out is None:
+        out, los = torch.empty((B, Ho, Wo, 2 * C), dtype=torch.bfloat16, device=x_cl.device), C
+    _lib.check(_lib.lib().mf_upsample_bilinear_cl_split_fwd(x_cl.data_ptr(), out[..., c_off:].data_ptr(), B, H, W, Ho, Wo,
+                                                            C, out.shape[3], los, _lib.stream_ptr()),
+               "mf_upsample_bilinear_cl_split_fwd")
+    return out
+
+
+def conv_split(xs, conv, res=None, act=0, slope=None, out32=True, outs=False):
+    """act(conv(x) + bias + res) of the split map xs [B, D, D, 2 Cin] with ``conv``'s weights (stride / padding /
+    dilation of the module) -> (fp32 [B, Do, Do, Cout] or None, split [B, Do, Do, 2 Cout] or None).  act: 0 none,
+    1 ReLU, 2 PReLU with the one-element tensor ``slope``; res: fp32 channels-last [B, Do, Do, Cout]."""
+    B, D, D2, C2 = xs.shape
+    Cout, Cin, k, _ = conv.weight.shape
+    if D2 != D or C2 != 2 * Cin or not xs.is_contiguous():
+        raise ValueError(f"conv_split: a contiguous square split map [B, D, D, {2 * Cin}] is required, got {tuple(xs.shape)}")
+    stride, pad, dil = conv.stride[0], conv.padding[0], conv.dilation[0]
+    Do = (D + 2 * pad - dil * (k - 1) - 1) // stride + 1
+    L = _lib.lib()
+    wp = split_pack(conv)
+    y32 = torch.empty((B, Do, Do, Cout), dtype=torch.float32, device=xs.device) if out32 else None
+    ys = torch.empty((B, Do, Do, 2 * Cout), dtype=torch.bfloat16, device=xs.device) if outs else None
+    nws = L.mf_conv2d_split_workspace_bytes(B, Cin, Cout, D, k, stride, pad, dil)
+    ws = torch.empty((nws,), dtype=torch.uint8, device=xs.device) if nws > 0 else None
+    bias = conv.bias.detach() if conv.bias is not None else None
+    _lib.check(L.mf_conv2d_split_fwd(xs.data_ptr(), wp.data_ptr(), _lib.ptr(bias), _lib.ptr(res),
+                                     res.stride(2) if res is not None else 0, _lib.ptr(slope), act, _lib.ptr(y32), Cout,
+                                     _lib.ptr(ys), 2 * Cout, Cout, _lib.ptr(ws), nws, B, Cin, Cout, D, k, stride, pad, dil,
+                                     _lib.stream_ptr()), "mf_conv2d_split_fwd")
+    return y32, ys
