@@ -16,7 +16,7 @@ SO_PATH = os.path.join(_HERE, os.path.basename(os.environ.get("MF_LIBMFHIP", "li
 _lib = None
 
 _p = ctypes.c_void_p
-_i = ctypes.c_int
+_i = ctypes.c_int32  # C int and int32_t: the same type on every ABI this library is built for
 _i64 = ctypes.c_int64
 _f = ctypes.c_float
 _d = ctypes.c_double
@@ -28,10 +28,8 @@ class IccBatch(ctypes.Structure):
     _fields_ = [
         ("pts4", _p), ("obj_off", _p), ("scene_off", _p), ("obj_scene", _p),
         ("pitch", _p), ("origin", _p), ("grid_target", _p), ("grid_ne", _p),
-        ("n_objects", ctypes.c_int32), ("n_scenes", ctypes.c_int32),
-        ("n_points", ctypes.c_int32), ("dim", ctypes.c_int32),
-        ("max_scene_objects", ctypes.c_int32),
-        ("voxel_threshold", _f), ("sdf_offset", _f), ("grid_ne_binary", ctypes.c_int32), ("flags", ctypes.c_int32),
+        ("n_objects", _i), ("n_scenes", _i), ("n_points", _i), ("dim", _i), ("max_scene_objects", _i),
+        ("voxel_threshold", _f), ("sdf_offset", _f), ("grid_ne_binary", _i), ("flags", _i),
     ]
 
 
@@ -39,7 +37,7 @@ class OccTree(ctypes.Structure):
     """mfOccTree (include/mfhip.h)."""
 
     _fields_ = [
-        ("logodds", _p), ("bits", _p), ("lo", ctypes.c_int32 * 3), ("dim", ctypes.c_int32 * 3),
+        ("logodds", _p), ("bits", _p), ("lo", _i * 3), ("dim", _i * 3),
         ("resolution", _d), ("res_factor", _d),
     ]
 
@@ -51,8 +49,7 @@ class IcpRegBatch(ctypes.Structure):
         "src", "src_off", "src_cnt", "tgt", "tgt_off", "tgt_cnt", "grid_off", "grid_dim", "grid_origin", "grid_start",
         "grid_idx", "transform_init", "active", "cur", "corr", "transform", "transformation", "fitness", "inlier_rmse",
         "n_iter", "hist_transform", "hist_fitness", "hist_rmse")] + [
-        ("max_corr_dist", _d), ("cell", _d), ("n_objects", ctypes.c_int32), ("max_iter", ctypes.c_int32),
-        ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+        ("max_corr_dist", _d), ("cell", _d), ("n_objects", _i), ("max_iter", _i), ("mode", _i), ("reserved", _i)]
 
 
 class MeshSdfBatch(ctypes.Structure):
@@ -61,8 +58,7 @@ class MeshSdfBatch(ctypes.Structure):
     _fields_ = [(n, _p) for n in (
         "vertices", "v_off", "faces", "f_off", "face_rec", "points", "q_off", "blk_off", "grid_origin", "grid_h",
         "dist", "face", "winding", "sdf", "occupancy")] + [
-        ("n_meshes", ctypes.c_int32), ("n_blocks", ctypes.c_int32), ("grid_dim", ctypes.c_int32),
-        ("reserved", ctypes.c_int32)]
+        ("n_meshes", _i), ("n_blocks", _i), ("grid_dim", _i), ("reserved", _i)]
 
 
 _SIGNATURES = {
@@ -81,115 +77,108 @@ _SIGNATURES = {
     "mf_pseudo_occupancy_weights": ([_p, _p, _p, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p], _i),
     "mf_nn": ([_p, _i64, _p, _i64, _p, _p, _p], _i),
     "mf_icp_loss_grad": ([_p, _i64, _p, _i64, _p, _f, _p, _p], _i),
-    "mf_icp_refine": ([_p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32, _f, _p, _p, _p, _p, ctypes.c_int32,
-                       ctypes.c_int32, _f, _f, _p, _p, _p], _i),
+    "mf_icp_refine": ([_p, _p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _i, _i, _f, _f, _p, _p, _p], _i),
     "mf_icc_workspace_bytes": ([ctypes.POINTER(IccBatch)], _i64),
     "mf_icc_iteration_launches": ([ctypes.POINTER(IccBatch)], _i),
-    "mf_icc_launch_stage": ([ctypes.POINTER(IccBatch), _p, _p, _p, ctypes.c_int32, _p], _i),
+    "mf_icc_launch_stage": ([ctypes.POINTER(IccBatch), _p, _p, _p, _i, _p], _i),
     "mf_icc_prepare": ([ctypes.POINTER(IccBatch), _p, _p], _i),
     "mf_icc_loss_grad": ([ctypes.POINTER(IccBatch), _p, _p, _p, _p, _p, _p, _p], _i),
-    "mf_icc_refine": ([ctypes.POINTER(IccBatch), _p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32, _f, _f, _p, _p, _p, _p], _i),
+    "mf_icc_refine": ([ctypes.POINTER(IccBatch), _p, _p, _p, _p, _i, _i, _f, _f, _p, _p, _p, _p], _i),
     "mf_icc_debug_stamps": ([_p, _i], _i),
-    "mf_sparse_conv3d_workspace_bytes": ([ctypes.c_int32] * 5 + [_i64], _i64),
-    "mf_sparse_conv3d_k4s2_points_fwd": ([_p, _p, _p, _i64, _f, _f, _f, _f, _p, _p, _p, _p, _p]
-                                         + [ctypes.c_int32] * 6 + [_p], _i),
-    "mf_sparse_conv3d_pack_weights": ([_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p], _i),
-    "mf_sparse_conv3d_k4s2_fwd": ([_p, _p, _p, _p, _p, _p, _p] + [ctypes.c_int32] * 6 + [_p], _i),
+    "mf_sparse_conv3d_workspace_bytes": ([_i] * 5 + [_i64], _i64),
+    "mf_sparse_conv3d_k4s2_points_fwd": ([_p, _p, _p, _i64, _f, _f, _f, _f, _p, _p, _p, _p, _p] + [_i] * 6 + [_p], _i),
+    "mf_sparse_conv3d_pack_weights": ([_p, _i, _i, _i, _i, _p, _p], _i),
+    "mf_sparse_conv3d_k4s2_fwd": ([_p, _p, _p, _p, _p, _p, _p] + [_i] * 6 + [_p], _i),
     "mf_pack_points_sdf": ([_p, _p, _i64, _p, _p], _i),
-    "mf_average_distance_fwd": ([_p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p, _p], _i),
-    "mf_average_distance_bwd": ([_p, _p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p, _p], _i),
-    "mf_conv3d_k4s2_pack_weights": ([_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p], _i),
-    "mf_conv3d_k4s2_default_split": ([ctypes.c_int32] * 4, ctypes.c_int32),
-    "mf_conv3d_k4s2_workspace_bytes": ([ctypes.c_int32] * 4, _i64),
-    "mf_conv3d_k4s2_fwd": ([_p, _p, _p, _p, _p, _p] + [ctypes.c_int32] * 6 + [_p], _i),
-    "mf_to_channels_last": ([_p, _p, ctypes.c_int32, ctypes.c_int32, _i64, _p], _i),
-    "mf_sparse_conv3d_k4s2_points_cl_fwd": ([_p, _i64, _p, _p, _i64, _f, _f, _f, _f, _p, _p, _p, _p, _p] + [ctypes.c_int32] * 6 + [_p], _i),
+    "mf_average_distance_fwd": ([_p, _p, _p, _p, _i, _i, _i, _p, _p, _p], _i),
+    "mf_average_distance_bwd": ([_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p], _i),
+    "mf_conv3d_k4s2_pack_weights": ([_p, _i, _i, _i, _i, _p, _p], _i),
+    "mf_conv3d_k4s2_default_split": ([_i] * 4, _i),
+    "mf_conv3d_k4s2_workspace_bytes": ([_i] * 4, _i64),
+    "mf_conv3d_k4s2_fwd": ([_p, _p, _p, _p, _p, _p] + [_i] * 6 + [_p], _i),
+    "mf_to_channels_last": ([_p, _p, _i, _i, _i64, _p], _i),
+    "mf_sparse_conv3d_k4s2_points_cl_fwd": ([_p, _i64, _p, _p, _i64, _f, _f, _f, _f, _p, _p, _p, _p, _p] + [_i] * 6 + [_p], _i),
     "mf_interpolate_voxel_grid_cl_fwd": ([_p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _i64, _p], _i),
-    "mf_occupancy_convs_fwd": ([_p] * 7 + [ctypes.c_int32] * 2 + [_p], _i),
-    "mf_linear_fwd": ([_p, _i64, ctypes.c_int32, _p, _i64, ctypes.c_int32, _p, _i64, _p, _i64] + [ctypes.c_int32] * 7 + [_p], _i),
-    "mf_cast_rows_bf16": ([_p, _i64, _p, _i64, _i64, ctypes.c_int32, _p], _i),
+    "mf_occupancy_convs_fwd": ([_p] * 7 + [_i] * 2 + [_p], _i),
+    "mf_linear_fwd": ([_p, _i64, _i, _p, _i64, _i, _p, _i64, _p, _i64] + [_i] * 7 + [_p], _i),
+    "mf_cast_rows_bf16": ([_p, _i64, _p, _i64, _i64, _i, _p], _i),
     "mf_relu_mask_bf16": ([_p, _p, _p, _p, _i64, _p], _i),
-    "mf_linear_bf16": ([_p, _i64, ctypes.c_int32, _p, _i64, ctypes.c_int32, _p, _i64, _p, _i64] + [ctypes.c_int32] * 8 + [_p], _i),
-    "mf_linear_wgrad_bf16": ([_p, _i64, ctypes.c_int32, _p, _i64, ctypes.c_int32, _p, _i64, ctypes.c_int32, _p]
-                             + [ctypes.c_int32] * 5 + [_p], _i),
-    "mf_conv3d_k4s2_pack_bf16": ([_p] + [ctypes.c_int32] * 4 + [_p, _p, _p], _i),
-    "mf_conv3d_k4s2_bf16_fwd": ([_p, _p, _p, _p] + [ctypes.c_int32] * 6 + [_p], _i),
-    "mf_conv3d_k4s2_bf16_dgrad": ([_p, _p, _p] + [ctypes.c_int32] * 6 + [_p], _i),
-    "mf_conv3d_k4s2_bf16_wgrad_workspace_bytes": ([ctypes.c_int32] * 3, _i64),
-    "mf_conv3d_k4s2_bf16_wgrad_default_split": ([ctypes.c_int32] * 4, ctypes.c_int32),
-    "mf_conv3d_k4s2_bf16_wgrad": ([_p, _p, _p, _p] + [ctypes.c_int32] * 7 + [_p], _i),
-    "mf_conv3d_bf16_pack": ([_p] + [ctypes.c_int32] * 5 + [_p, _p, _p, _p], _i),
-    "mf_conv3d_bf16_fwd": ([_p, _p, _p, _p] + [ctypes.c_int32] * 11 + [_p], _i),
-    "mf_conv3d_bf16_fwd_workspace_bytes": ([ctypes.c_int32] * 8, _i64),
-    "mf_conv3d_bf16_fwd_ws": ([_p, _p, _p, _p, _p, _i64] + [ctypes.c_int32] * 11 + [_p], _i),
-    "mf_conv2d_split_pack": ([_p] + [ctypes.c_int32] * 3 + [_p, _p], _i),
-    "mf_conv2d_split_workspace_bytes": ([ctypes.c_int32] * 8, _i64),
-    "mf_conv2d_split_fwd": ([_p, _p, _p, _p, ctypes.c_int32, _p, ctypes.c_int32, _p, ctypes.c_int32, _p, ctypes.c_int32,
-                             ctypes.c_int32, _p, _i64] + [ctypes.c_int32] * 8 + [_p], _i),
-    "mf_conv3d_k3_narrow_bf16_pack_elems": ([ctypes.c_int32], _i64),
-    "mf_conv3d_k3_narrow_bf16_pack": ([_p] + [ctypes.c_int32] * 5 + [_p, _p], _i),
-    "mf_conv3d_k3_narrow_bf16": ([_p, _p, _p, _p] + [ctypes.c_int32] * 6 + [_p], _i),
-    "mf_conv3d_bf16_wgrad_workspace_bytes": ([ctypes.c_int32] * 4, _i64),
+    "mf_linear_bf16": ([_p, _i64, _i, _p, _i64, _i, _p, _i64, _p, _i64] + [_i] * 8 + [_p], _i),
+    "mf_linear_wgrad_bf16": ([_p, _i64, _i, _p, _i64, _i, _p, _i64, _i, _p] + [_i] * 5 + [_p], _i),
+    "mf_conv3d_k4s2_pack_bf16": ([_p] + [_i] * 4 + [_p, _p, _p], _i),
+    "mf_conv3d_k4s2_bf16_fwd": ([_p, _p, _p, _p] + [_i] * 6 + [_p], _i),
+    "mf_conv3d_k4s2_bf16_dgrad": ([_p, _p, _p] + [_i] * 6 + [_p], _i),
+    "mf_conv3d_k4s2_bf16_wgrad_workspace_bytes": ([_i] * 3, _i64),
+    "mf_conv3d_k4s2_bf16_wgrad_default_split": ([_i] * 4, _i),
+    "mf_conv3d_k4s2_bf16_wgrad": ([_p, _p, _p, _p] + [_i] * 7 + [_p], _i),
+    "mf_conv3d_bf16_pack": ([_p] + [_i] * 5 + [_p, _p, _p, _p], _i),
+    "mf_conv3d_bf16_fwd": ([_p, _p, _p, _p] + [_i] * 11 + [_p], _i),
+    "mf_conv3d_bf16_fwd_workspace_bytes": ([_i] * 8, _i64),
+    "mf_conv3d_bf16_fwd_ws": ([_p, _p, _p, _p, _p, _i64] + [_i] * 11 + [_p], _i),
+    "mf_conv2d_split_pack": ([_p] + [_i] * 3 + [_p, _p], _i),
+    "mf_conv2d_split_workspace_bytes": ([_i] * 8, _i64),
+    "mf_conv2d_split_fwd": ([_p, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _i, _p, _i64] + [_i] * 8 + [_p], _i),
+    "mf_conv3d_k3_narrow_bf16_pack_elems": ([_i], _i64),
+    "mf_conv3d_k3_narrow_bf16_pack": ([_p] + [_i] * 5 + [_p, _p], _i),
+    "mf_conv3d_k3_narrow_bf16": ([_p, _p, _p, _p] + [_i] * 6 + [_p], _i),
+    "mf_conv3d_bf16_wgrad_workspace_bytes": ([_i] * 4, _i64),
     "mf_wgrad_split": ([_i64, _i64, _i64], _i),
-    "mf_linear_wgrad_bf16_default_split": ([_i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32], ctypes.c_int32),
-    "mf_conv3d_bf16_wgrad_default_split": ([ctypes.c_int32] * 5, ctypes.c_int32),
-    "mf_conv3d_bf16_wgrad": ([_p, _p, _p, _p] + [ctypes.c_int32] * 11 + [_p], _i),
+    "mf_linear_wgrad_bf16_default_split": ([_i64, _i, _i, _i], _i),
+    "mf_conv3d_bf16_wgrad_default_split": ([_i] * 5, _i),
+    "mf_conv3d_bf16_wgrad": ([_p, _p, _p, _p] + [_i] * 11 + [_p], _i),
     "mf_sparse_conv3_bf16_max_rows": ([_i64], _i64),
-    "mf_sparse_conv3_bf16_workspace_bytes": ([_i64, ctypes.c_int32, ctypes.c_int32], _i64),
-    "mf_sparse_conv3_bf16_tables": ([_p, _i64, ctypes.c_int32, ctypes.c_int32, _p], _i),
-    "mf_sparse_conv3_bf16_index": ([_p, _p, _i64, ctypes.c_int32, ctypes.c_int32, _p, _p], _i),
-    "mf_sparse_conv3_bf16_pack": ([_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p, _p], _i),
-    "mf_sparse_conv3_bf16_unpack_dw": ([_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p], _i),
-    "mf_sparse_conv3_bf16_reduce": ([_p, _p, _p, _p, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p], _i),
-    "mf_sparse_conv3_bf16_gather_dy": ([_p, _p, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p], _i),
-    "mf_linear_bf16_tiles": ([_p, ctypes.c_int32, _p, _i64, ctypes.c_int32, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p], _i),
-    "mf_linear_wgrad_bf16_ranges": ([_p, ctypes.c_int32, _p, ctypes.c_int32, _p, _i64, ctypes.c_int32, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p], _i),
-    "mf_conv3d_k4s2_bf16_pack_cols": ([_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p], _i),
-    "mf_conv3d_k4s2_bf16_col2im": ([_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p], _i),
-    "mf_average_voxelization_rows_bf16_fwd": ([_p, _i64, _p, _p, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p, _p, _p, _p, _i64, _p], _i),
-    "mf_average_voxelization_rows_bf16_bwd": ([_p, _i64, _p, _p, _p, _p, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _i64, _p], _i),
-    "mf_average_voxelization_cl_bf16_fwd": ([_p, _i64, _p, _p, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _i64,
-                                             _p, _p, _p, _p], _i),
-    "mf_average_voxelization_cl_bf16_bwd": ([_p, _i64, _p, _p, _p, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p,
-                                             _i64, _p], _i),
+    "mf_sparse_conv3_bf16_workspace_bytes": ([_i64, _i, _i], _i64),
+    "mf_sparse_conv3_bf16_tables": ([_p, _i64, _i, _i, _p], _i),
+    "mf_sparse_conv3_bf16_index": ([_p, _p, _i64, _i, _i, _p, _p], _i),
+    "mf_sparse_conv3_bf16_pack": ([_p, _i, _i, _i, _i, _p, _p, _p], _i),
+    "mf_sparse_conv3_bf16_unpack_dw": ([_p, _i, _i, _i, _i, _p, _p], _i),
+    "mf_sparse_conv3_bf16_reduce": ([_p, _p, _p, _p, _i64, _i, _i, _i, _i, _p, _p], _i),
+    "mf_sparse_conv3_bf16_gather_dy": ([_p, _p, _i64, _i, _i, _i, _p, _p], _i),
+    "mf_linear_bf16_tiles": ([_p, _i, _p, _i64, _i, _p, _p, _i, _i, _i, _i, _i, _p], _i),
+    "mf_linear_wgrad_bf16_ranges": ([_p, _i, _p, _i, _p, _i64, _i, _p, _i, _i, _i, _p], _i),
+    "mf_conv3d_k4s2_bf16_pack_cols": ([_p, _i, _i, _i, _i, _p, _p], _i),
+    "mf_conv3d_k4s2_bf16_col2im": ([_p, _i, _i, _i, _p, _p], _i),
+    "mf_average_voxelization_rows_bf16_fwd": ([_p, _i64, _p, _p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _i64, _p], _i),
+    "mf_average_voxelization_rows_bf16_bwd": ([_p, _i64, _p, _p, _p, _p, _i64, _i, _i, _i, _p, _i64, _p], _i),
+    "mf_average_voxelization_cl_bf16_fwd": ([_p, _i64, _p, _p, _i64, _i, _i, _i, _p, _i64, _p, _p, _p, _p], _i),
+    "mf_average_voxelization_cl_bf16_bwd": ([_p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p, _i64, _p], _i),
     "mf_interpolate_voxel_grid_cl_bf16_fwd": ([_p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _i64, _p], _i),
     "mf_interpolate_voxel_grid_cl_bf16_bwd": ([_p, _i64, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _i, _p], _i),
-    "mf_upsample_bilinear_cl_fwd": ([_p, _p] + [ctypes.c_int32] * 7 + [_p], _i),
-    "mf_upsample_bilinear_cl_split_fwd": ([_p, _p] + [ctypes.c_int32] * 8 + [_p], _i),
-    "mf_split_bf16": ([_p, _i64, _i64, _i64, _i64] + [ctypes.c_int32] * 4 + [_p, ctypes.c_int32, ctypes.c_int32, _p], _i),
-    "mf_upsample_bilinear_cl_bwd": ([_p, _p] + [ctypes.c_int32] * 7 + [_p], _i),
-    "mf_upsample_bilinear_cf_fwd": ([_p, _p, _i64] + [ctypes.c_int32] * 5 + [_p], _i),
-    "mf_upsample_bilinear_cf_bwd": ([_p, _p, _i64] + [ctypes.c_int32] * 5 + [_p], _i),
-    "mf_prelu_fwd": ([_p, _p, _p, _i64, ctypes.c_int32, _p], _i),
-    "mf_rgb_normalize": ([_p, ctypes.c_int32, _p, _p, _p, _i64, _p], _i),
-    "mf_bn_act_fwd": ([_p, _p, _p, _p, _p, _p, ctypes.c_float, _p, _i64, ctypes.c_int32, _i64, ctypes.c_int32,
-                       ctypes.c_int32, ctypes.c_int32, _p], _i),
+    "mf_upsample_bilinear_cl_fwd": ([_p, _p] + [_i] * 7 + [_p], _i),
+    "mf_upsample_bilinear_cl_split_fwd": ([_p, _p] + [_i] * 8 + [_p], _i),
+    "mf_split_bf16": ([_p, _i64, _i64, _i64, _i64] + [_i] * 4 + [_p, _i, _i, _p], _i),
+    "mf_upsample_bilinear_cl_bwd": ([_p, _p] + [_i] * 7 + [_p], _i),
+    "mf_upsample_bilinear_cf_fwd": ([_p, _p, _i64] + [_i] * 5 + [_p], _i),
+    "mf_upsample_bilinear_cf_bwd": ([_p, _p, _i64] + [_i] * 5 + [_p], _i),
+    "mf_prelu_fwd": ([_p, _p, _p, _i64, _i, _p], _i),
+    "mf_rgb_normalize": ([_p, _i, _p, _p, _p, _i64, _p], _i),
+    "mf_bn_act_fwd": ([_p, _p, _p, _p, _p, _p, _f, _p, _i64, _i, _i64, _i, _i, _i, _p], _i),
     "mf_prelu_bwd_workspace_floats": ([_i64], _i64),
-    "mf_prelu_bwd": ([_p, _p, _p, _p, _p, _p, _i64, ctypes.c_int32, _p], _i),
+    "mf_prelu_bwd": ([_p, _p, _p, _p, _p, _p, _i64, _i, _p], _i),
     "mf_gemm_bf16_last_tile": ([], _i),
-    "mf_psp_tail_rows_bf16_fwd": ([_p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p], _i),
-    "mf_psp_tail_rows_bf16_bwd": ([_p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p, _p], _i),
-    "mf_confidence_loss_fwd": ([_p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _p, _p, _p], _i),
-    "mf_confidence_loss_bwd": ([_p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _p, _p, _p], _i),
-    "mf_pose_epilogue_train_fwd": ([_p, _p, _p, _p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p, _p, _p], _i),
-    "mf_pose_epilogue_train_bwd": ([_p, _p, _p, _p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p, _p, _p], _i),
+    "mf_psp_tail_rows_bf16_fwd": ([_p, _p, _i, _i, _i, _i, _p, _p], _i),
+    "mf_psp_tail_rows_bf16_bwd": ([_p, _p, _i, _i, _i, _i, _p, _p, _p], _i),
+    "mf_confidence_loss_fwd": ([_p, _p, _i, _i, _f, _p, _p, _p], _i),
+    "mf_confidence_loss_bwd": ([_p, _p, _p, _p, _i, _i, _f, _p, _p, _p], _i),
+    "mf_pose_epilogue_train_fwd": ([_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p], _i),
+    "mf_pose_epilogue_train_bwd": ([_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p], _i),
     "mf_transformation_matrix_fwd": ([_p, _p, _i64, _p, _p], _i),
     "mf_transformation_matrix_bwd": ([_p, _p, _i64, _p, _p, _p], _i),
-    "mf_point_prep": ([_p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _f, _p, _p, _p, _p, _p], _i),
-    "mf_pose_epilogue": ([_p, _i64, ctypes.c_int32, _p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p, _p, _p], _i),
-    "mf_psp_tail_fwd": ([_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p] + [ctypes.c_int32] * 4 + [_p, _p], _i),
-    "mf_valid_pixel_order": ([_p, ctypes.c_int32, ctypes.c_int32, _p, _p, _p], _i),
+    "mf_point_prep": ([_p, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p], _i),
+    "mf_pose_epilogue": ([_p, _i64, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p], _i),
+    "mf_psp_tail_fwd": ([_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p] + [_i] * 4 + [_p, _p], _i),
+    "mf_valid_pixel_order": ([_p, _i, _i, _p, _p, _p], _i),
     "mf_instance_stats": ([_p, _p, _i, _i, _p, _i, _p, _p], _i),
     "mf_instance_crops": ([_p, _p, _p, _i, _i, _d, _d, _d, _d, _p, _p, _i, _i, _i, _p, _p, _p, _p], _i),
     "mf_occmap_regrid": ([ctypes.POINTER(OccTree), ctypes.POINTER(OccTree), _p], _i),
-    "mf_occmap_bounds": ([_p, _p, _i64, _p, ctypes.c_int32, _p, ctypes.c_int32, _p, _p], _i),
-    "mf_occmap_raycast": ([_p, _p, _i64, _p, ctypes.c_int32, _p, _f, _f, _f, _p, _p], _i),
-    "mf_occmap_count_hits": ([_p, _i64, _p, ctypes.c_int32, _p, _p], _i),
-    "mf_occmap_apply": ([_p, ctypes.c_int32, _i64, ctypes.c_int32, _p], _i),
-    "mf_occmap_extract": ([_p, ctypes.c_int32, _p, _p, _p] + [ctypes.c_int32] * 4 + [_p] * 6, _i),
+    "mf_occmap_bounds": ([_p, _p, _i64, _p, _i, _p, _i, _p, _p], _i),
+    "mf_occmap_raycast": ([_p, _p, _i64, _p, _i, _p, _f, _f, _f, _p, _p], _i),
+    "mf_occmap_count_hits": ([_p, _i64, _p, _i, _p, _p], _i),
+    "mf_occmap_apply": ([_p, _i, _i64, _i, _p], _i),
+    "mf_occmap_extract": ([_p, _i, _p, _p, _p] + [_i] * 4 + [_p] * 6, _i),
     "mf_icpreg_workspace_bytes": ([_i64, _i64, _i64], _i64),
-    "mf_icpreg_bounds": ([_p, _p, ctypes.c_int32, _d, _p, _p, _p], _i),
-    "mf_icpreg_prepare": ([_p, _p, ctypes.c_int32, _d, _p, _p, _p, _i64, _p, _p, _i64, _d, _i64] + [_p] * 7, _i),
+    "mf_icpreg_bounds": ([_p, _p, _i, _d, _p, _p, _p], _i),
+    "mf_icpreg_prepare": ([_p, _p, _i, _d, _p, _p, _p, _i64, _p, _p, _i64, _d, _i64] + [_p] * 7, _i),
     "mf_icpreg_run": ([ctypes.POINTER(IcpRegBatch), _p], _i),
     "mf_meshsdf_workspace_bytes": ([_i64], _i64),
     "mf_meshsdf_prepare": ([ctypes.POINTER(MeshSdfBatch), _i64, _p], _i),
@@ -197,6 +186,16 @@ _SIGNATURES = {
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+
+
+def bind(handle, partial=False):
+    """Set ``argtypes`` / ``restype`` of every ``_SIGNATURES`` entry on a ``ctypes.CDLL`` and return it.  A missing
+    symbol raises, unless ``partial``: a library built from a few of the csrc files binds the ones it has."""
+    for name, (argtypes, restype) in _SIGNATURES.items():
+        fn = getattr(handle, name, None) if partial else getattr(handle, name)  # AttributeError: symbol absent
+        if fn is not None:
+            fn.argtypes, fn.restype = argtypes, restype
+    return handle
 
 
 def lib():
@@ -209,11 +208,7 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C "
                 "morefusion_amd/csrc`). morefusion_amd has no CPU fallback."
             )
-        handle = ctypes.CDLL(SO_PATH)
-        for name, (argtypes, restype) in _SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if a declared symbol is absent
-            fn.argtypes = argtypes
-            fn.restype = restype
+        handle = bind(ctypes.CDLL(SO_PATH))
         _lib = handle
     return _lib
 

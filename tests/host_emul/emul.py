@@ -9,25 +9,12 @@ import subprocess
 
 import numpy as np
 
+from morefusion_amd import _lib
+
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CSRC = os.path.join(ROOT, "morefusion_amd", "csrc")
 HERE = os.path.dirname(os.path.abspath(__file__))
 BUILD = os.path.join(HERE, "_build")
-
-_p, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-
-
-class IccBatch(ctypes.Structure):
-    """mfIccBatch (include/mfhip.h) -- same layout as morefusion_amd/_lib.py."""
-
-    _fields_ = [
-        ("pts4", _p), ("obj_off", _p), ("scene_off", _p), ("obj_scene", _p),
-        ("pitch", _p), ("origin", _p), ("grid_target", _p), ("grid_ne", _p),
-        ("n_objects", ctypes.c_int32), ("n_scenes", ctypes.c_int32),
-        ("n_points", ctypes.c_int32), ("dim", ctypes.c_int32),
-        ("max_scene_objects", ctypes.c_int32),
-        ("voxel_threshold", _f), ("sdf_offset", _f), ("grid_ne_binary", ctypes.c_int32), ("flags", ctypes.c_int32),
-    ]
 
 
 def available():
@@ -35,7 +22,8 @@ def available():
 
 
 def build(sources, extra_flags=()):
-    """Compile the given csrc/*.hip files with g++ behind the emulator shim -> ctypes library."""
+    """Compile the given csrc/*.hip files with g++ behind the emulator shim -> ctypes library, bound like the
+    product's (``_lib.bind``; only the symbols of the given files exist)."""
     os.makedirs(BUILD, exist_ok=True)
     h = hashlib.sha1()
     for name in list(sources) + ["mf_common.h"]:
@@ -66,7 +54,22 @@ def build(sources, extra_flags=()):
                        check=True)
         os.replace(os.path.join(work, "lib.so"), so)
         shutil.rmtree(work, ignore_errors=True)
-    return ctypes.CDLL(so)
+    return _lib.bind(ctypes.CDLL(so), partial=True)
+
+
+def patch_lib(L, monkeypatch=None):
+    """Point the product's operator wrappers at the emulated library ``L`` (or a proxy of it): ``_lib.lib()`` returns
+    it, tensors need not be on a GPU, there is no stream, and a failing call raises with the wrapper's own text.
+    With pytest's ``monkeypatch`` the change is undone after the test; without one it lasts for the process."""
+    def check(code, what):
+        if code:
+            raise RuntimeError(what)
+    for name, value in (("lib", lambda: L), ("require_gpu", lambda *a: None), ("stream_ptr", lambda: None),
+                        ("check", check)):
+        if monkeypatch is None:
+            setattr(_lib, name, value)
+        else:
+            monkeypatch.setattr(_lib, name, value)
 
 
 def ptr(a):
@@ -78,12 +81,6 @@ class EmulIccScenes:
 
     def __init__(self, lib, scenes, voxel_dim=32, voxel_threshold=2, sdf_offset=0.0, single_pass=None):
         self.lib = lib
-        lib.mf_icc_workspace_bytes.restype = _i64
-        P = ctypes.POINTER(IccBatch)
-        lib.mf_icc_workspace_bytes.argtypes = [P]
-        lib.mf_icc_prepare.argtypes = [P, _p, _p]
-        lib.mf_icc_loss_grad.argtypes = [P, _p, _p, _p, _p, _p, _p, _p]
-        lib.mf_icc_refine.argtypes = [P, _p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32, _f, _f, _p, _p, _p, _p]
         pts, sdf, obj_off, scene_off, obj_scene = [], [], [0], [0], []
         pitch, origin, gt, gne = [], [], [], []
         for s, sc in enumerate(scenes):
@@ -108,7 +105,7 @@ class EmulIccScenes:
         self.origin = np.ascontiguousarray(np.concatenate(origin))
         self.grid_target = np.ascontiguousarray(np.concatenate(gt))
         self.grid_ne = np.ascontiguousarray(np.concatenate(gne))
-        self.desc = IccBatch(
+        self.desc = _lib.IccBatch(
             ptr(self.pts4), ptr(self.obj_off), ptr(self.scene_off), ptr(self.obj_scene), ptr(self.pitch),
             ptr(self.origin), ptr(self.grid_target), ptr(self.grid_ne), self.n_objects, self.n_scenes,
             self.n_points, voxel_dim, max(scene_off[i + 1] - scene_off[i] for i in range(len(scenes))),

@@ -17,7 +17,6 @@
 
 Every tensor any of these kernels is handed -- inputs, packed weights, scratch, workspaces, outputs -- sits
 against an inaccessible page on the named side (emul.GuardedTensors)."""
-import ctypes
 import os
 import sys
 
@@ -30,26 +29,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 from host_emul import emul  # noqa: E402
 
 
-def _bind(L):
-    from morefusion_amd import _lib
-    for name, (argtypes, restype) in _lib._SIGNATURES.items():
-        fn = getattr(L, name, None)
-        if fn is not None:
-            fn.argtypes, fn.restype = argtypes, restype
-
-
-def _patch_lib(G):
-    from morefusion_amd import _lib
-    _lib.lib = lambda: G
-    _lib.require_gpu = lambda *a: None
-    _lib.stream_ptr = lambda: None
-
-    def check(code, what):
-        if code:
-            raise RuntimeError(what)
-    _lib.check = check
-
-
 def volumetric(side):
     from oracle import oracle_c as OC
     import morefusion_amd as mf
@@ -57,7 +36,6 @@ def volumetric(side):
     from morefusion_amd.contrib.singleview_3d.models import Model
 
     L = emul.build(["conv3d.hip", "sparseconv.hip", "interp.hip", "linear.hip", "pointops.hip"])
-    _bind(L)
 
     def avg_cpu(values, points, batch_indices, *, batch_size, origin, pitch, dimensions, return_counts=False, **kw):
         m, c = OC.average_voxelization_3d(values.numpy(), points.numpy(), batch_indices.numpy(),
@@ -101,7 +79,7 @@ def volumetric(side):
         model.sparse_conv3 = True
         log = open(os.environ.get("MF_GUARD_LOG", os.devnull), "w")
         with emul.GuardedTensors(L, side, log) as G:
-            _patch_lib(G)
+            emul.patch_lib(G)
             got = model._pose_from_features_cl(class_id, values, points_cam, pitch, origin, grid)
             ncalls = G.calls
     assert ncalls >= 15, ncalls
@@ -115,7 +93,6 @@ def frontend(side):
     from morefusion_amd.models.backbone2d import PSPNetExtractor
     from morefusion_amd.contrib.singleview_3d.models import Model
     L = emul.build(["psp_tail.hip", "preprocess.hip"])
-    _bind(L)
     torch.manual_seed(0)
     log = open(os.environ.get("MF_GUARD_LOG", os.devnull), "w")
     net = PSPNetExtractor().eval()
@@ -134,7 +111,7 @@ def frontend(side):
             x = u2.contiguous(memory_format=fmt)
             net.up2 = torch.nn.Identity()
             with emul.GuardedTensors(L, side, log) as G:
-                _patch_lib(G)
+                emul.patch_lib(G)
                 out = net.forward_sampled_rows(x, pix)
             np.testing.assert_allclose(out.numpy(), ref.numpy(), rtol=0, atol=2e-5)
     # valid-pixel order (Model._select_points): ragged counts, an image without NaNs, one with a single valid pixel
@@ -147,7 +124,7 @@ def frontend(side):
         pcd[2, Hh - 1, Ww - 1] = 0.5
         t = torch.from_numpy(pcd)
         with emul.GuardedTensors(L, side, log) as G:
-            _patch_lib(G)
+            emul.patch_lib(G)
             got = m._select_points(t)
         for i in range(3):
             valid = np.flatnonzero(~np.isnan(pcd[i]).any(-1))
@@ -168,7 +145,7 @@ def frontend(side):
     Kmat = np.array([[80.0, 0, 36.0], [0, 80.0, 30.0], [0, 0, 1]])
     ids = np.array([1, 2, 3, 7], np.int32)   # 7: no pixel at all
     with emul.GuardedTensors(L, side, log) as G:
-        _patch_lib(G)
+        emul.patch_lib(G)
         out = instance_crops(torch.from_numpy(rgb), torch.from_numpy(depth), Kmat, torch.from_numpy(label), ids,
                              image_size=S, min_valid=20)
     w_rgb, w_pcd, w_keep, _ = O.instance_crops(rgb, depth, Kmat, label, ids, image_size=S, min_valid=20)
@@ -193,10 +170,9 @@ def training(side):
     from morefusion_amd.contrib.singleview_3d.models import bf16_ops
     import test_emul_bf16_ops as T   # the test bodies: operators vs torch float32 autograd / the oracle
     L = emul.build(["gemm_bf16.hip", "voxelize.hip", "interp.hip"])
-    _bind(L)
     log = open(os.environ["MF_GUARD_LOG"], "w") if os.environ.get("MF_GUARD_LOG") else None
     with emul.GuardedTensors(L, side, log) as G:
-        _patch_lib(G)
+        emul.patch_lib(G)
         T.test_conv3d_operator_forward_and_gradients(bf16_ops)
         # both forms of the occupancy branch behind the guard pages: the narrow voxels-as-columns kernel (its padding taps
         # are masked buffer loads) and the implicit-GEMM engine

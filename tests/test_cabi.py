@@ -11,15 +11,77 @@ import morefusion_amd as mf
 from conftest import ROOT
 
 
-def _declared():
-    text = open(os.path.join(ROOT, "include", "mfhip.h")).read()
+HEADER = os.path.join(ROOT, "include", "mfhip.h")
+STRUCTS = {"mfIccBatch": mf._lib.IccBatch, "mfOccTree": mf._lib.OccTree, "mfIcpRegBatch": mf._lib.IcpRegBatch,
+           "mfMeshSdfBatch": mf._lib.MeshSdfBatch}
+SCALARS = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+           "double": ctypes.c_double, "mfStream_t": ctypes.c_void_p}
+
+
+def _parse_header(text):
+    """-> ({function: (return type, [argument declaration, ...])}, {struct: [field declaration, ...]})"""
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(mf_[a-z0-9_]+)\s*\(", text)))
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    struct_re = r"typedef struct \{(.*?)\} (\w+);"
+    structs = {name: [d.strip() for d in body.split(";") if d.strip()]
+               for body, name in re.findall(struct_re, text, re.S)}
+    protos = {name: (ret.strip(), [] if args.strip() in ("", "void") else [a.strip() for a in args.split(",")])
+              for ret, name, args in re.findall(r"([\w\s*]+?)\b(mf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;",
+                                                re.sub(struct_re, "", text, flags=re.S))}
+    return protos, structs
+
+
+def _ctypes_of(decl, named=True):
+    """C declaration (``const float *x``, ``int32_t lo[3]``; ``named=False``: a return type) -> (name, the ctypes a
+    binding may use for it).  One rule: scalars by width, every pointer ``c_void_p``, a pointer to a descriptor struct
+    also ``POINTER(<its Structure>)`` (``c_void_p``: a device array of descriptors), ``const char *`` returned
+    ``c_char_p``."""
+    type_part, name, dim = re.fullmatch(r"(.*?)(\w+)(?:\[(\d+)\])?", decl).groups() if named else (decl, None, None)
+    words = [w for w in re.findall(r"\w+|\*", type_part) if w != "const"]
+    if "*" in words:
+        assert words.count("*") == 1 and dim is None, decl
+        if words[0] in STRUCTS:
+            return name, {ctypes.POINTER(STRUCTS[words[0]]), ctypes.c_void_p}
+        return name, {ctypes.c_char_p if words[0] == "char" and not named else ctypes.c_void_p}
+    assert len(words) == 1 and words[0] in SCALARS, f"no rule for `{decl}`"
+    return name, {SCALARS[words[0]] * int(dim) if dim else SCALARS[words[0]]}
+
+
+def _abi_mismatches(header_text):
+    """Every place where morefusion_amd/_lib.py (``_SIGNATURES``, the four Structures) differs from the header."""
+    protos, structs = _parse_header(header_text)
+    table, bad = mf._lib._SIGNATURES, []
+    bad += [f"{n}: declared, not bound" for n in sorted(set(protos) - set(table))]
+    bad += [f"{n}: bound, not declared" for n in sorted(set(table) - set(protos))]
+    for name in sorted(set(protos) & set(table)):
+        (ret, args), (argtypes, restype) = protos[name], table[name]
+        if restype not in _ctypes_of(ret, named=False)[1]:
+            bad.append(f"{name}: returns `{ret}`, bound as {restype.__name__}")
+        if len(args) != len(argtypes):
+            bad.append(f"{name}: {len(args)} arguments declared, {len(argtypes)} bound")
+            continue
+        bad += [f"{name}: argument {k} `{decl}` bound as {t.__name__}"
+                for k, (decl, t) in enumerate(zip(args, argtypes)) if t not in _ctypes_of(decl)[1]]
+    for cname, cls in STRUCTS.items():
+        fields = [_ctypes_of(d) for d in structs[cname]]
+        if [n for n, _ in fields] != [f[0] for f in cls._fields_]:
+            bad.append(f"{cname}: fields {[n for n, _ in fields]} declared, {[f[0] for f in cls._fields_]} bound")
+            continue
+        bad += [f"{cname}.{n}: bound as {f[1].__name__}" for (n, allowed), f in zip(fields, cls._fields_)
+                if f[1] not in allowed]
+        size = align = 0
+        for _, allowed in fields:  # natural alignment: each field at a multiple of its element size, tail padded
+            t = next(iter(allowed))  # (a pointer's alternatives have one size)
+            a = ctypes.sizeof(getattr(t, "_type_", t)) if hasattr(t, "_length_") else ctypes.sizeof(t)
+            size, align = -(-size // a) * a + ctypes.sizeof(t), max(align, a)
+        if ctypes.sizeof(cls) != -(-size // align) * align:
+            bad.append(f"{cname}: {-(-size // align) * align} bytes declared, {ctypes.sizeof(cls)} bound")
+    return bad
 
 
 def test_library_exports_every_declared_symbol():
     lib = mf._lib.lib()  # dlopen works without a GPU
-    declared = _declared()
+    declared = sorted(_parse_header(open(HEADER).read())[0])
     assert len(declared) >= 24
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/mfhip.h but not exported"
@@ -28,10 +90,30 @@ def test_library_exports_every_declared_symbol():
     assert isinstance(lib.mf_last_error_string(), bytes)
 
 
+def test_binding_types_match_header():
+    """Argument count, every argument type, the return type of all entry points and the layout of the four
+    descriptor structs: an ``int64_t`` bound as ``int`` would not raise, it would hand a kernel a garbage size."""
+    assert _abi_mismatches(open(HEADER).read()) == []
+
+
+def test_binding_check_reports_a_doctored_header():
+    """The comparator is not vacuous: a narrowed argument, a dropped argument and a renamed struct field are each
+    reported, by name, and nothing else is."""
+    text = open(HEADER).read()
+    for old, new in (("const float *ref, int64_t R,", "const float *ref, int32_t R,"),
+                     ("int64_t n, void *pts4,", "int64_t n,"),
+                     ("double res_factor;", "double inv_resolution;")):
+        assert text.count(old) == 1
+        text = text.replace(old, new)
+    bad = _abi_mismatches(text)
+    assert len(bad) == 3, bad
+    assert any(b.startswith("mf_nn: argument 1 `int32_t R`") for b in bad), bad
+    assert any(b.startswith("mf_pack_points_sdf: 4 arguments declared, 5 bound") for b in bad), bad
+    assert any(b.startswith("mfOccTree: fields") and "inv_resolution" in b for b in bad), bad
+
+
 def test_icc_batch_struct_matches_header():
-    text = open(os.path.join(ROOT, "include", "mfhip.h")).read()
-    body = text[text.index("typedef struct {"):text.index("} mfIccBatch;")]
-    fields = re.findall(r"\b(\w+);", body)
+    fields = [_ctypes_of(d)[0] for d in _parse_header(open(HEADER).read())[1]["mfIccBatch"]]
     assert fields == [f[0] for f in mf._lib.IccBatch._fields_]
     assert ctypes.sizeof(mf._lib.IccBatch) == 8 * 8 + 5 * 4 + 2 * 4 + 4 + 4 + 4  # (+ flags, + tail padding to 8)
 
@@ -97,11 +179,8 @@ def test_wgrad_split_cost_model_is_a_host_function_with_sane_answers():
     of 128 x 128 output tiles, 64-row K-tiles and the slab size.  conv3 at the training batch (160 tiles, 1024
     K-tiles) fills exactly one round of the chip's 512 workgroup slots with 3 slabs (4 would spill a quarter-full
     second round); conv4 (512 tiles) needs none; tiny layers split deep but keep >= 8 K-tiles per slab."""
-    import ctypes
     from morefusion_amd import _lib
     L = _lib.lib()
-    L.mf_wgrad_split.argtypes = [ctypes.c_int64] * 3
-    L.mf_wgrad_split.restype = ctypes.c_int32
     assert L.mf_wgrad_split(160, 1024, 256 * 10240 * 4) == 3
     assert L.mf_wgrad_split(512, 128, 512 * 16384 * 4) == 1
     assert L.mf_wgrad_split(120, 250, 1920 * 984 * 4) == 4

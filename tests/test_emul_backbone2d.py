@@ -13,17 +13,9 @@ pytestmark = pytest.mark.skipif(not emul.available(), reason="g++ not available"
 
 @pytest.fixture()
 def ops(monkeypatch):
-    from morefusion_amd import _lib
     from morefusion_amd.models import ops2d
     L = emul.build(["backbone2d.hip"])
-    for name, (argtypes, restype) in _lib._SIGNATURES.items():
-        fn = getattr(L, name, None)
-        if fn is not None:
-            fn.argtypes, fn.restype = argtypes, restype
-    monkeypatch.setattr(_lib, "lib", lambda: L)
-    monkeypatch.setattr(_lib, "require_gpu", lambda *a: None)
-    monkeypatch.setattr(_lib, "stream_ptr", lambda: None)
-    monkeypatch.setattr(_lib, "check", lambda code, what: (_ for _ in ()).throw(RuntimeError(what)) if code else None)
+    emul.patch_lib(L, monkeypatch)
     return ops2d
 
 

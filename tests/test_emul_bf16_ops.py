@@ -13,17 +13,9 @@ pytestmark = pytest.mark.skipif(not emul.available(), reason="g++ not available"
 
 @pytest.fixture()
 def K(monkeypatch):
-    from morefusion_amd import _lib
     from morefusion_amd.contrib.singleview_3d.models import bf16_ops
     L = emul.build(["gemm_bf16.hip"])
-    for name, (argtypes, restype) in _lib._SIGNATURES.items():
-        fn = getattr(L, name, None)
-        if fn is not None:
-            fn.argtypes, fn.restype = argtypes, restype
-    monkeypatch.setattr(_lib, "lib", lambda: L)
-    monkeypatch.setattr(_lib, "require_gpu", lambda *a: None)
-    monkeypatch.setattr(_lib, "stream_ptr", lambda: None)
-    monkeypatch.setattr(_lib, "check", lambda code, what: (_ for _ in ()).throw(RuntimeError(what)) if code else None)
+    emul.patch_lib(L, monkeypatch)
     return bf16_ops
 
 
@@ -126,17 +118,9 @@ def test_linear_operator_forward_and_gradients(K, n, Kin, N, relu):
 @pytest.fixture()
 def KV(monkeypatch):
     """bf16_ops over the emulated voxelize / interp / gemm sources."""
-    from morefusion_amd import _lib
     from morefusion_amd.contrib.singleview_3d.models import bf16_ops
     L = emul.build(["gemm_bf16.hip", "voxelize.hip", "interp.hip"])
-    for name, (argtypes, restype) in _lib._SIGNATURES.items():
-        fn = getattr(L, name, None)
-        if fn is not None:
-            fn.argtypes, fn.restype = argtypes, restype
-    monkeypatch.setattr(_lib, "lib", lambda: L)
-    monkeypatch.setattr(_lib, "require_gpu", lambda *a: None)
-    monkeypatch.setattr(_lib, "stream_ptr", lambda: None)
-    monkeypatch.setattr(_lib, "check", lambda code, what: (_ for _ in ()).throw(RuntimeError(what)) if code else None)
+    emul.patch_lib(L, monkeypatch)
     return bf16_ops
 
 
@@ -226,17 +210,9 @@ def test_channels_last_bf16_voxelization_and_sampling_vs_oracle(KV):
 @pytest.fixture()
 def KS(monkeypatch):
     """bf16_ops over the emulated engines + the sparse conv3 kernels + the voxelization kernels."""
-    from morefusion_amd import _lib
     from morefusion_amd.contrib.singleview_3d.models import bf16_ops
     L = emul.build(["gemm_bf16.hip", "sparseconv_bf16.hip", "voxelize.hip"])
-    for name, (argtypes, restype) in _lib._SIGNATURES.items():
-        fn = getattr(L, name, None)
-        if fn is not None:
-            fn.argtypes, fn.restype = argtypes, restype
-    monkeypatch.setattr(_lib, "lib", lambda: L)
-    monkeypatch.setattr(_lib, "require_gpu", lambda *a: None)
-    monkeypatch.setattr(_lib, "stream_ptr", lambda: None)
-    monkeypatch.setattr(_lib, "check", lambda code, what: (_ for _ in ()).throw(RuntimeError(what)) if code else None)
+    emul.patch_lib(L, monkeypatch)
     return bf16_ops
 
 
@@ -306,17 +282,9 @@ def test_sparse_conv3_operator_forward_and_all_gradients_vs_dense_float32(KS, wi
 
 @pytest.fixture()
 def KP(monkeypatch):
-    from morefusion_amd import _lib
     from morefusion_amd.contrib.singleview_3d.models import bf16_ops
     L = emul.build(["pointops.hip"])
-    for name, (argtypes, restype) in _lib._SIGNATURES.items():
-        fn = getattr(L, name, None)
-        if fn is not None:
-            fn.argtypes, fn.restype = argtypes, restype
-    monkeypatch.setattr(_lib, "lib", lambda: L)
-    monkeypatch.setattr(_lib, "require_gpu", lambda *a: None)
-    monkeypatch.setattr(_lib, "stream_ptr", lambda: None)
-    monkeypatch.setattr(_lib, "check", lambda code, what: (_ for _ in ()).throw(RuntimeError(what)) if code else None)
+    emul.patch_lib(L, monkeypatch)
     return bf16_ops
 
 
@@ -373,16 +341,10 @@ def test_training_pose_epilogue_forward_and_gradients(KP):
 def test_confidence_loss_forward_and_gradients(monkeypatch):
     """functions.loss.confidence_loss (csrc/loss.hip k_conf_loss_fwd / _bwd) vs the torch composite of
     model.py:417-434, incl. non-confident points (conf <= 0) and an object without any (NaN, zero gradients)."""
-    from morefusion_amd import _lib
     import importlib
     CL = importlib.import_module("morefusion_amd.functions.loss.confidence_loss")
     L = emul.build(["loss.hip"])
-    for name, (argtypes, restype) in _lib._SIGNATURES.items():
-        fn = getattr(L, name, None)
-        if fn is not None:
-            fn.argtypes, fn.restype = argtypes, restype
-    monkeypatch.setattr(_lib, "lib", lambda: L)
-    monkeypatch.setattr(_lib, "stream_ptr", lambda: None)
+    emul.patch_lib(L, monkeypatch)
     torch.manual_seed(3)
     for B, P, dead in ((5, 333, False), (18, 70, False), (3, 100, True)):
         add = torch.rand(B, P, requires_grad=True)
@@ -409,17 +371,9 @@ def test_sampled_pspnet_tail_training_rows_vs_torch_formulation(monkeypatch):
     """PSPNetExtractor._tail_rows_bf16 (csrc/psp_tail.hip k_tail_rows_fwd / _bwd + the bf16 GEMM engines + the PReLU
     kernel) vs the float32 torch formulation ``_tail`` (taps, four gathers, einsum, conv1d, log-softmax): the window
     rows bit-for-bit against the same arithmetic in torch, the features and every gradient within bf16 tolerance."""
-    from morefusion_amd import _lib
     from morefusion_amd.models import backbone2d, ops2d
     L = emul.build(["psp_tail.hip", "gemm_bf16.hip", "backbone2d.hip"])
-    for name, (argtypes, restype) in _lib._SIGNATURES.items():
-        fn = getattr(L, name, None)
-        if fn is not None:
-            fn.argtypes, fn.restype = argtypes, restype
-    monkeypatch.setattr(_lib, "lib", lambda: L)
-    monkeypatch.setattr(_lib, "require_gpu", lambda *a: None)
-    monkeypatch.setattr(_lib, "stream_ptr", lambda: None)
-    monkeypatch.setattr(_lib, "check", lambda code, what: (_ for _ in ()).throw(RuntimeError(what)) if code else None)
+    emul.patch_lib(L, monkeypatch)
     torch.manual_seed(11)
     B, H, W, P = 2, 8, 12, 48
     net = backbone2d.PSPNetExtractor()

@@ -2,7 +2,6 @@
 behind the fiber emulator (tests/host_emul) and checked against torch's dense Conv3d -- the operator the
 reference applies there (contrib/singleview_3d/models/model.py:73-74,128,139: Convolution3D(.., 4, 2, pad=1)).
 fp32 sums in a different order: tolerance 2e-5 of the largest output."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -15,15 +14,7 @@ pytestmark = pytest.mark.skipif(not emul.available(), reason="g++ not available"
 
 @pytest.fixture(scope="module")
 def lib():
-    L = emul.build(["conv3d.hip"])
-    i32, p = ctypes.c_int32, ctypes.c_void_p
-    L.mf_conv3d_k4s2_pack_weights.argtypes = [p, i32, i32, i32, i32, p, p]
-    L.mf_conv3d_k4s2_workspace_bytes.restype = ctypes.c_int64
-    L.mf_conv3d_k4s2_workspace_bytes.argtypes = [i32] * 4
-    L.mf_conv3d_k4s2_default_split.argtypes = [i32] * 4
-    L.mf_conv3d_k4s2_fwd.argtypes = [p] * 6 + [i32] * 6 + [p]
-    L.mf_to_channels_last.argtypes = [p, p, i32, i32, ctypes.c_int64, p]
-    return L
+    return emul.build(["conv3d.hip"])
 
 
 def _run(L, x_cf, W, bias, add_cl, split, relu, c_off=0, cin=None):
@@ -103,8 +94,6 @@ def test_to_channels_last(lib):
 
 def test_occupancy_convs_match_torch(lib):
     """conv1_occ (1 -> 8, k3 p1) + ReLU + conv2_occ (8 -> 16, k3 dilation 2 p2) + ReLU, channels-last out."""
-    i32, p = ctypes.c_int32, ctypes.c_void_p
-    lib.mf_occupancy_convs_fwd.argtypes = [p] * 7 + [i32] * 2 + [p]
     rs = np.random.RandomState(3)
     B, D = 2, 6
     grid = (rs.uniform(size=(B, D, D, D)) < 0.4).astype(np.float32)
@@ -131,8 +120,6 @@ def test_linear_mfma_gemm_vs_float64():
     """csrc/linear.hip: grouped row-major GEMM + bias + ReLU (the heads' 1x1 convolutions on points-major rows):
     K not a multiple of 32, M not a multiple of 128, N < Npad, column-block inputs / outputs, two groups."""
     L = emul.build(["linear.hip"])
-    i32, i64, p = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
-    L.mf_linear_fwd.argtypes = [p, i64, i32, p, i64, i32, p, i64, p, i64] + [i32] * 7 + [p]
     rs = np.random.RandomState(4)
     M, K, N, Npad, groups = 150, 72, 84, 128, 2
     lda, ldo = 200, 300
@@ -186,9 +173,6 @@ def test_point_prep_and_pose_epilogue_vs_numpy():
     epilogue (class selection, chainer's normalize, translation, sigmoid) against the torch expressions of
     contrib/singleview_3d/models/model.py:236,101,262-273 restated in NumPy float32."""
     L = emul.build(["pointops.hip"])
-    i32, i64, p, f = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_float
-    L.mf_point_prep.argtypes = [p, p, p, p, i32, i32, i32, f, p, p, p, p, p]
-    L.mf_pose_epilogue.argtypes = [p, i64, i32, p, p, p, p, i32, i32, i32, p, p, p, p]
     rs = np.random.RandomState(9)
     B, P, Cv = 3, 70, 8
     n = B * P
@@ -237,8 +221,6 @@ def test_psp_tail_kernel_vs_torch_formulation():
     channels-last source maps, image-border pixels (zero padding of the 3x3 convolution) included."""
     from morefusion_amd.models.backbone2d import PSPNetExtractor
     L = emul.build(["psp_tail.hip"])
-    i32, i64, p = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
-    L.mf_psp_tail_fwd.argtypes = [p, i64, i64, i64, i64, p, p, p, p, p, p] + [i32] * 4 + [p, p]
     torch.manual_seed(0)
     net = PSPNetExtractor().eval()
     with torch.no_grad():

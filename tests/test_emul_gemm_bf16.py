@@ -18,13 +18,7 @@ pytestmark = pytest.mark.skipif(not emul.available(), reason="g++ not available"
 
 @pytest.fixture(scope="module")
 def L():
-    from morefusion_amd import _lib
-    lib = emul.build(["gemm_bf16.hip"])
-    for name, (argtypes, restype) in _lib._SIGNATURES.items():
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.argtypes, fn.restype = argtypes, restype
-    return lib
+    return emul.build(["gemm_bf16.hip"])
 
 
 @pytest.fixture(params=["tile128", "tile256"], autouse=True)

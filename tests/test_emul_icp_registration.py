@@ -18,17 +18,9 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 @pytest.fixture()
 def M(monkeypatch):
-    from morefusion_amd import _lib
     from morefusion_amd.contrib import icp_registration as mod
     L = emul.build(["icpreg.hip"])
-    for name, (argtypes, restype) in _lib._SIGNATURES.items():
-        fn = getattr(L, name, None)
-        if fn is not None:
-            fn.argtypes, fn.restype = argtypes, restype
-    monkeypatch.setattr(_lib, "lib", lambda: L)
-    monkeypatch.setattr(_lib, "require_gpu", lambda *a: None)
-    monkeypatch.setattr(_lib, "stream_ptr", lambda: None)
-    monkeypatch.setattr(_lib, "check", lambda code, what: (_ for _ in ()).throw(RuntimeError(what)) if code else None)
+    emul.patch_lib(L, monkeypatch)
     mod.clear_cache()
     yield mod
     mod.clear_cache()

@@ -17,17 +17,9 @@ ORIGIN2 = (0.05, -0.1, -0.08)
 
 @pytest.fixture()
 def M(monkeypatch):
-    from morefusion_amd import _lib
     from morefusion_amd.contrib import multi_instance_octree_mapping as mod
     L = emul.build(["occmap.hip"])
-    for name, (argtypes, restype) in _lib._SIGNATURES.items():
-        fn = getattr(L, name, None)
-        if fn is not None:
-            fn.argtypes, fn.restype = argtypes, restype
-    monkeypatch.setattr(_lib, "lib", lambda: L)
-    monkeypatch.setattr(_lib, "require_gpu", lambda *a: None)
-    monkeypatch.setattr(_lib, "stream_ptr", lambda: None)
-    monkeypatch.setattr(_lib, "check", lambda code, what: (_ for _ in ()).throw(RuntimeError(what)) if code else None)
+    emul.patch_lib(L, monkeypatch)
     return mod
 
 

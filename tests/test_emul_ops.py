@@ -1,7 +1,6 @@
 """Kernel SOURCES other than the ICC compiled for the host behind tests/host_emul (fiber emulator)
 and checked against the oracle without a GPU: the fused ADD / ADD-S loss (csrc/loss.hip) and
 interpolate_voxel_grid with per-item row ranges (csrc/interp.hip)."""
-import ctypes
 import os
 import sys
 
@@ -14,7 +13,6 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hos
 import emul  # noqa: E402
 
 pytestmark = pytest.mark.skipif(not emul.available(), reason="g++ not available")
-_p, _i32 = ctypes.c_void_p, ctypes.c_int32
 
 
 def _pose(rs):
@@ -27,8 +25,6 @@ def _pose(rs):
 
 def test_add_loss_kernel_source_vs_oracle():
     lib = emul.build(["loss.hip"])
-    lib.mf_average_distance_fwd.argtypes = [_p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p]
-    lib.mf_average_distance_bwd.argtypes = [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p]
     rs = np.random.RandomState(0)
     B, M, P = 3, 300, 5
     pts = rs.uniform(-0.05, 0.05, (B, M, 3)).astype(np.float32)
@@ -92,7 +88,6 @@ def test_add_loss_kernel_source_vs_oracle():
 @pytest.mark.parametrize("channels_first", [0, 1])
 def test_interpolate_kernel_source_row_ranges_vs_oracle(channels_first):
     lib = emul.build(["interp.hip"])
-    lib.mf_interpolate_voxel_grid_fwd.argtypes = [_p, _p, _p, _p, ctypes.c_int64] + [ctypes.c_int] * 5 + [_p, ctypes.c_int, _p]
     rs = np.random.RandomState(1)
     B, C, X = 3, 6, 8
     counts = [120, 0, 77]
@@ -120,7 +115,6 @@ def test_interpolate_voxel_major_kernel_source_vs_oracle(C):
     gather per 4 channels): bit-identical to the oracle's GPU-order sums, both output layouts,
     with and without row ranges."""
     lib = emul.build(["interp.hip"])
-    lib.mf_interpolate_voxel_grid_fwd.argtypes = [_p, _p, _p, _p, ctypes.c_int64] + [ctypes.c_int] * 5 + [_p, ctypes.c_int, _p]
     rs = np.random.RandomState(2)
     B, X = 2, 8
     counts = [37, 21]
@@ -148,8 +142,6 @@ def test_fused_icp_loop_kernel_source_vs_oracle(fixtures3):
     from conftest import golden
     from oracle import oracle_c as OC
     lib = emul.build(["occgrid_knn.hip"])
-    lib.mf_icp_refine.argtypes = [_p, _p, _p, _p, _i32, _i32, ctypes.c_float, _p, _p, _p, _p, _i32, _i32,
-                                  ctypes.c_float, ctypes.c_float, _p, _p, _p]
     g = golden("oracle_icc_icp_trajectories.npz")
     links = []
     for f in (fixtures3[2], fixtures3[0]):
@@ -189,7 +181,6 @@ def test_valid_pixel_order_kernel_source_vs_numpy_where():
     np.where(~isnan(pcd).any(-1)) (model.py:195-196,206): vector-load and scalar paths, a ragged
     tail, an image without valid pixels, +-inf coordinates (valid: only NaN masks a pixel)."""
     lib = emul.build(["preprocess.hip"])
-    lib.mf_valid_pixel_order.argtypes = [_p, _i32, _i32, _p, _p, _p]
     rs = np.random.RandomState(3)
     for HW, off in ((4096 + 2048, 0), (5003, 0), (4096, 1), (4096 * 6 + 8, 0), (4096 * 2 + 5, 1)):
         B = 3
@@ -218,12 +209,6 @@ def test_sparse_conv3_kernel_sources_vs_dense_conv():
     import torch
     from oracle import oracle_np as O_
     lib = emul.build(["sparseconv.hip"])
-    i64 = ctypes.c_int64
-    lib.mf_sparse_conv3d_workspace_bytes.restype = i64
-    lib.mf_sparse_conv3d_workspace_bytes.argtypes = [_i32] * 5 + [i64]
-    lib.mf_sparse_conv3d_pack_weights.argtypes = [_p, _i32, _i32, _i32, _i32, _p, _p]
-    lib.mf_sparse_conv3d_k4s2_points_fwd.argtypes = [_p, _p, _p, i64] + [ctypes.c_float] * 4 + [_p] * 5 + [_i32] * 6 + [_p]
-    lib.mf_sparse_conv3d_k4s2_fwd.argtypes = [_p] * 7 + [_i32] * 6 + [_p]
     rs = np.random.RandomState(5)
     B, Cs, Cout, D, n = 2, 8, 64, 8, 70
     points = rs.uniform(-0.6, D - 0.4, (n, 3)).astype(np.float32)
@@ -261,11 +246,6 @@ def test_voxelize_kernel_sources_vs_reference_cuda_text():
     average fwd + bwd and max fwd + bwd, bit-exact (round-half-away, intensity ties)."""
     from conftest import golden
     lib = emul.build(["voxelize.hip"])
-    i64, f = ctypes.c_int64, ctypes.c_float
-    lib.mf_average_voxelization_3d_fwd.argtypes = [_p, _p, _p, i64] + [ctypes.c_int] * 5 + [f] * 4 + [_p] * 6
-    lib.mf_average_voxelization_3d_bwd.argtypes = [_p, _p, _p, _p, i64] + [ctypes.c_int] * 5 + [f] * 4 + [_p, _p]
-    lib.mf_max_voxelization_3d_fwd.argtypes = [_p, _p, _p, _p, i64] + [ctypes.c_int] * 5 + [f] * 4 + [_p] * 5
-    lib.mf_max_voxelization_3d_bwd.argtypes = [_p, _p, i64] + [ctypes.c_int] * 5 + [_p, _p]
     g = golden("ref_cuda_voxelization.npz")
     D, B = int(g["dim"]), int(g["batch_size"])
     values, points, bi = (np.ascontiguousarray(g[k]) for k in ("values", "points", "batch_indices"))
@@ -307,9 +287,6 @@ def test_tdf_kernel_sources_vs_reference_cuda_text(tag):
     text: distances and winner indices bit-exact, backward to float-atomic tolerance."""
     from conftest import golden
     lib = emul.build(["tdf.hip"])
-    i64, f, ci = ctypes.c_int64, ctypes.c_float, ctypes.c_int
-    lib.mf_truncated_distance_function_fwd.argtypes = [_p, i64, f, f, f, f, ci, ci, ci, f, _p, _p, _p]
-    lib.mf_truncated_distance_function_bwd.argtypes = [_p, _p, _p, i64, f, f, f, f, ci, ci, ci, f, _p, _p]
     g = golden("ref_cuda_tdf.npz")
     c = {k.split("__", 1)[1]: g[k] for k in g if k.startswith(tag + "__")}
     X, Y, Z = (int(v) for v in c["dims"])
@@ -335,8 +312,6 @@ def test_tdf_kernel_with_more_points_than_one_register_chunk():
     points outside the grid, vs the C oracle: distances and winner ids bit-exact."""
     from oracle import oracle_c as OC
     lib = emul.build(["tdf.hip"])
-    i64, f, ci = ctypes.c_int64, ctypes.c_float, ctypes.c_int
-    lib.mf_truncated_distance_function_fwd.argtypes = [_p, i64, f, f, f, f, ci, ci, ci, f, _p, _p, _p]
     rs = np.random.RandomState(5)
     dims, pitch, origin = (16, 12, 20), 0.01, (-0.08, -0.06, -0.1)
     pts = rs.uniform(-0.1, 0.12, (6000, 3)).astype(np.float32)
@@ -357,17 +332,13 @@ def test_nn_and_interpolate_kernel_sources_vs_reference_cuda_text():
     """k_nn (occgrid_knn.hip) against the reference's RawKernel + argmin, and interp.hip forward /
     backward against its K5 / K6 text (tests/golden/ref_cuda_nn.npz, ref_cuda_interpolate.npz)."""
     from conftest import golden
-    i64, ci = ctypes.c_int64, ctypes.c_int
     lib = emul.build(["occgrid_knn.hip"])
-    lib.mf_nn.argtypes = [_p, i64, _p, i64, _p, _p, _p]
     g = golden("ref_cuda_nn.npz")
     ref, query = np.ascontiguousarray(g["ref"]), np.ascontiguousarray(g["query"])
     out = np.zeros(len(query), np.int64)
     assert lib.mf_nn(ref.ctypes.data, len(ref), query.ctypes.data, len(query), out.ctypes.data, None, None) == 0
     np.testing.assert_array_equal(out, g["indices"])
     lib = emul.build(["interp.hip"])
-    lib.mf_interpolate_voxel_grid_fwd.argtypes = [_p, _p, _p, _p, i64] + [ci] * 5 + [_p, ci, _p]
-    lib.mf_interpolate_voxel_grid_bwd.argtypes = [_p, _p, _p, _p, i64] + [ci] * 5 + [_p, ci, _p]
     g = golden("ref_cuda_interpolate.npz")
     vox, pts, bi = (np.ascontiguousarray(g[k]) for k in ("voxelized", "points", "batch_indices"))
     B, C, X = vox.shape[0], vox.shape[1], vox.shape[2]
@@ -389,9 +360,7 @@ def test_occupancy_grid_and_loss_kernel_sources_vs_reference_outputs():
     ADD / ADD-S loss kernels (loss.hip) against the reference's average_distance executed
     (ref_cuda_average_distance.npz: values + gradient to the predicted transforms)."""
     from conftest import golden
-    i64, f, ci = ctypes.c_int64, ctypes.c_float, ctypes.c_int
     lib = emul.build(["occgrid_knn.hip"])
-    lib.mf_occupancy_grid_3d_fwd.argtypes = [_p, i64, f, f, f, f, ci, ci, ci, f, _p, _p, _p]
     g = golden("ref_occupancy_grid_3d.npz")
     pts = np.ascontiguousarray(g["known_points"])
     grid, dmin = np.zeros((5, 5, 5), np.float32), np.zeros((5, 5, 5), np.float32)
@@ -406,8 +375,6 @@ def test_occupancy_grid_and_loss_kernel_sources_vs_reference_outputs():
     np.testing.assert_array_equal(grid, g["c1_grid_thr2"])
 
     lib = emul.build(["loss.hip"])
-    lib.mf_average_distance_fwd.argtypes = [_p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p]
-    lib.mf_average_distance_bwd.argtypes = [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p]
     g = golden("ref_cuda_average_distance.npz")
     pts, Tt, Tp = (np.ascontiguousarray(g[k]) for k in ("points", "transform_true", "transforms_pred"))
     M, P = len(pts), len(Tp)
@@ -431,14 +398,6 @@ def test_channels_last_sparse_conv3_and_sampler_give_the_channels_first_bits():
     reading whole voxel rows and writing into a column block of a wider matrix) against the channels-first
     kernels they stand beside: bit-identical results (same taps / corners in the same order)."""
     lib = emul.build(["sparseconv.hip", "interp.hip"])
-    i64, f = ctypes.c_int64, ctypes.c_float
-    lib.mf_sparse_conv3d_workspace_bytes.restype = i64
-    lib.mf_sparse_conv3d_workspace_bytes.argtypes = [_i32] * 5 + [i64]
-    lib.mf_sparse_conv3d_pack_weights.argtypes = [_p, _i32, _i32, _i32, _i32, _p, _p]
-    lib.mf_sparse_conv3d_k4s2_points_fwd.argtypes = [_p, _p, _p, i64] + [f] * 4 + [_p] * 5 + [_i32] * 6 + [_p]
-    lib.mf_sparse_conv3d_k4s2_points_cl_fwd.argtypes = [_p, i64, _p, _p, i64] + [f] * 4 + [_p] * 5 + [_i32] * 6 + [_p]
-    lib.mf_interpolate_voxel_grid_fwd.argtypes = [_p, _p, _p, _p, i64] + [ctypes.c_int] * 5 + [_p, ctypes.c_int, _p]
-    lib.mf_interpolate_voxel_grid_cl_fwd.argtypes = [_p, _p, _p, i64] + [ctypes.c_int] * 5 + [_p, i64, _p]
     rs = np.random.RandomState(11)
     B, Cs, Cout, D, n, ld = 2, 8, 256, 8, 90, 20
     points = rs.uniform(-0.6, D - 0.4, (n, 3)).astype(np.float32)

@@ -6,7 +6,7 @@ import os
 import numpy as np
 import torch
 
-from morefusion_amd import geometry, synthetic
+from morefusion_amd import _lib, geometry, synthetic
 from oracle import oracle_np as O
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -103,9 +103,7 @@ def test_crop_kernel_source_on_the_host_matches_oracle(tmp_path):
     so = tmp_path / "libpre_host.so"
     subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
                     "-I", os.path.join(root, "include"), "-o", str(so), str(src)], check=True)
-    L = ctypes.CDLL(str(so))
-    p, i, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-    L.mf_instance_crops.argtypes = [p, p, p, i, i, d, d, d, d, p, p, i, i, i, p, p, p, p]
+    L = _lib.bind(ctypes.CDLL(str(so)), partial=True)
     for seed, (H, W), S in [(0, (480, 640), 256), (2, (300, 420), 256), (3, (480, 640), 64)]:
         f = synthetic.make_rgbd_frame(seed, H, W)
         ids = f["instance_ids"]
