@@ -113,12 +113,20 @@ class Conv3d(torch.autograd.Function):
         def narrow(ci, co):
             return (ks == 3 and stride == 1 and pad == dil and ci in (8, 16) and 4 <= co <= 16 and co % 4 == 0
                     and D & (D - 1) == 0 and c_off == 0 and os.environ.get("MF_NARROW_CONV", "1") != "0")
-        nar_f, nar_d = narrow(Cin, Cout), need_dx and narrow(Cout, Cin)
+        nar_f = narrow(Cin, Cout)
+        # a narrow layer that writes 4 or 12 channels: the kernels of the backward pass read their operands in chunks
+        # of 8 channels, so the output gradient travels with Cp = 8 or 16 columns (zeros beyond Cout) against a weight
+        # of Cp output channels (zero rows beyond Cout) -- the data gradient is then a narrow convolution itself
+        Cp = -(-Cout // 8) * 8 if nar_f else Cout
+        nar_d = need_dx and narrow(Cp, Cin)
 
         def build_narrow(transpose):
             w = weight.detach().float().contiguous()
-            wp = _empty((int(L.mf_conv3d_k3_narrow_bf16_pack_elems(Cout if transpose else Cin)),), BF16, x)
-            _lib.check(L.mf_conv3d_k3_narrow_bf16_pack(w.data_ptr(), Cout, Cin, w_cin, c_off, int(transpose), wp.data_ptr(),
+            if transpose and Cp != Cout:
+                w = torch.cat((w, w.new_zeros((Cp - Cout,) + tuple(w.shape[1:]))))
+            co = Cp if transpose else Cout
+            wp = _empty((int(L.mf_conv3d_k3_narrow_bf16_pack_elems(co if transpose else Cin)),), BF16, x)
+            _lib.check(L.mf_conv3d_k3_narrow_bf16_pack(w.data_ptr(), co, Cin, w_cin, c_off, int(transpose), wp.data_ptr(),
                                                        _lib.stream_ptr()), "mf_conv3d_k3_narrow_bf16_pack")
             return wp
 
@@ -129,11 +137,10 @@ class Conv3d(torch.autograd.Function):
             b = bias.detach().float().contiguous() if bias is not None else None
             _lib.check(L.mf_conv3d_k3_narrow_bf16(x.data_ptr(), wpf.data_ptr(), _lib.ptr(b), out.data_ptr(), B, Cin, Cout, D,
                                                   dil, int(relu), _lib.stream_ptr()), "mf_conv3d_k3_narrow_bf16")
-            wf = None
-            if need_dx and not nar_d:
-                wf = _cached_pack(weight, ("conv3d_flipT", Cin, x.device.index), lambda: build()[2])
-            ctx.save_for_backward(x, None, wf, out if relu else None, wpd)
+            # (a narrow forward's data gradient is always narrow: Cp in {8, 16} read, Cin in {8, 16} written)
+            ctx.save_for_backward(x, None, None, out if relu else None, wpd)
             ctx.geom = (B, Cin, Cout, D, Do, ks, stride, pad, dil, w_cin, c_off, bool(relu), bias is not None, weight.shape)
+            ctx.Cp = Cp
             return out
 
         def build():
@@ -156,6 +163,7 @@ class Conv3d(torch.autograd.Function):
                                            _lib.stream_ptr()), "mf_conv3d_bf16_fwd_ws")
         ctx.save_for_backward(x, wd, None if nar_d else wf, out if relu else None, wpd)
         ctx.geom = (B, Cin, Cout, D, Do, ks, stride, pad, dil, w_cin, c_off, bool(relu), bias is not None, weight.shape)
+        ctx.Cp = Cout
         return out
 
     @staticmethod
@@ -165,6 +173,14 @@ class Conv3d(torch.autograd.Function):
         L = _lib.lib()
         dz = relu_mask(out, dy) if relu else _bf16c(dy)
         dx = dw = db = None
+        if has_bias and ctx.needs_input_grad[2]:
+            db = dz.reshape(-1, Cout).sum(dim=0, dtype=torch.float32)
+        n_out = Cout
+        if ctx.Cp != Cout:  # (a narrow layer of 4 / 12 output channels: zero columns / zero weight rows up to Cp)
+            dzp = torch.zeros((B, Do ** 3, ctx.Cp), dtype=BF16, device=dz.device)
+            dzp[:, :, :Cout] = dz
+            dz, Cout = dzp, ctx.Cp
+            wshape = (Cout,) + tuple(wshape[1:])
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             if wpd is not None:  # narrow 3 x 3 x 3 layer: the same kernel on the transposed / flipped pack
@@ -186,8 +202,8 @@ class Conv3d(torch.autograd.Function):
             _lib.check(L.mf_conv3d_bf16_wgrad(dz.data_ptr(), x.data_ptr(), dw.data_ptr(), ws.data_ptr(), B, Cin, Cout, D,
                                               ks, stride, pad, dil, w_cin, c_off, split, _lib.stream_ptr()),
                        "mf_conv3d_bf16_wgrad")
-        if has_bias and ctx.needs_input_grad[2]:
-            db = dz.reshape(-1, Cout).sum(dim=0, dtype=torch.float32)
+            if Cout != n_out:
+                dw = dw[:n_out].contiguous()
         return dx, dw, db, None, None, None, None
 
 

@@ -178,6 +178,8 @@ def training(side):
         # are masked buffer loads) and the implicit-GEMM engine
         for narrow in (True, False):
             T.test_occupancy_branch_operator_chain(bf16_ops, _MonkeyPatch(), narrow)
+        # a narrow layer of 12 written channels with its input gradient: the output gradient travels zero-padded to 16
+        T.test_conv3d_operator_narrow_layers_of_4_and_12_channels(bf16_ops, _MonkeyPatch(), 8, 12, 4, 1)
         for n, Kin, N, relu in ((150, 3, 8, True), (130, 64, 63, False), (70, 200, 136, True)):
             T.test_linear_operator_forward_and_gradients.__wrapped__(bf16_ops, n, Kin, N, relu) if hasattr(
                 T.test_linear_operator_forward_and_gradients, "__wrapped__") else \

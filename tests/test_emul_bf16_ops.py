@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import bf16_bound as BB
+import bf16_cases as C
 from host_emul import emul
 
 pytestmark = pytest.mark.skipif(not emul.available(), reason="g++ not available")
@@ -40,6 +42,8 @@ def test_conv3d_operator_forward_and_gradients(K):
     y.backward(g.float().reshape(B, D // 2, D // 2, D // 2, Cout).permute(0, 4, 1, 2, 3))
     y_cl = y.detach().permute(0, 2, 3, 4, 1).reshape(B, -1, Cout)
     assert rel(out, y_cl) < 2 ** -7
+    r64 = BB.conv_ref(x.detach(), wr.detach(), conv.bias.detach(), D, (4, 2, 1, 1))   # every element, derived bound
+    BB.assert_within(out, F.relu(r64["y"]), r64["Sy"], 64 * Cin + 1, "Conv3d k4s2 operator fwd")
     assert rel(x.grad, xr.grad.permute(0, 2, 3, 4, 1).reshape(B, -1, Cin)) < 2e-2   # (bf16 output + mask flips at 0)
     assert rel(conv.weight.grad[:, c_off:c_off + Cin], wr.grad) < 2e-2
     assert float(conv.weight.grad[:, :c_off].abs().max()) == 0.0
@@ -92,6 +96,53 @@ def test_occupancy_branch_operator_chain(K, monkeypatch, narrow):
     assert calls == ([(8, 8, D, 1), (8, 16, D, 2), (16, 8, D, 2)] if narrow else [])
 
 
+@pytest.mark.parametrize("B,CI,CO,D,dil", [(3, 8, 4, 2, 1), (1, 8, 12, 4, 2), (1, 16, 12, 4, 3), (2, 16, 4, 8, 1),
+                                           (5, 16, 16, 2, 1), (1, 8, 16, 8, 2)])
+def test_narrow_kernel_per_element(K, B, CI, CO, D, dil):
+    """k_conv_k3_narrow_bf16 directly, every element under the derived bound (tests/bf16_bound.py): written channels 4
+    and 12, a partial last tile (B D^3 = 24 and 40 voxels for tiles of 32), a dilation at or beyond D (every tap but
+    the centre is padding), forward with bias + ReLU and the data gradient through the transposed pack."""
+    L = K._lib.lib()
+    C.narrow_case(L, "cpu", lambda: None, B, CI, CO, D, dil, what="emul narrow")
+    C.narrow_case(L, "cpu", lambda: None, B, CI, CO, D, dil, transpose=True, what="emul narrow")
+
+
+def test_narrow_kernel_single_real_input_channel_and_refusals(K):
+    """conv1_occ's form: 8 channels travel, the weight has one (w_cin = 1); whatever the other 7 hold is not read."""
+    L = K._lib.lib()
+    C.narrow_case(L, "cpu", lambda: None, 1, 8, 8, 4, 1, w_cin=1, what="emul narrow")
+    C.narrow_refusal_case(L, "cpu", lambda: None)
+
+
+@pytest.mark.parametrize("Cin,Cout,D,dil", [(8, 12, 4, 1), (16, 4, 8, 2)])
+def test_conv3d_operator_narrow_layers_of_4_and_12_channels(K, monkeypatch, Cin, Cout, D, dil):
+    """Conv3d on a narrow layer whose written channels are not 8 / 16, with the input gradient wanted: the forward, the
+    data gradient and the weight gradient (the output gradient travels zero-padded to 8 / 16 channels), all on the
+    narrow kernel / the TN engine, per element.  (The operator used to reference its pack builder before defining
+    it here: NameError.)"""
+    monkeypatch.setenv("MF_NARROW_CONV", "1")
+    Lh = K._lib.lib()
+    calls = []
+    real = Lh.mf_conv3d_k3_narrow_bf16
+    monkeypatch.setattr(Lh, "mf_conv3d_k3_narrow_bf16", lambda *a: (calls.append(a[5:9]), real(*a))[1], raising=False)
+    C.op_conv3d_case(K, "cpu", 1, Cin, Cout, D, (3, 1, dil, dil), what="emul Conv3d")
+    Cp = -(-Cout // 8) * 8
+    assert calls == [(Cin, Cout, D, dil), (Cp, Cin, D, dil)]   # forward, data gradient
+
+
+@pytest.mark.parametrize("D,geom", [(10, (3, 1, 0, 1)), (9, (4, 1, 1, 1))], ids=["k3p0_D10", "k4p1_D9"])
+def test_conv3d_operator_refuses_input_gradient_when_input_grid_is_not_a_power_of_two(K, D, geom):
+    """Stride 1 with D = 10 / 9 -> 8: forward and weight gradient exist; the data gradient would be a convolution
+    whose OUTPUT is the 10^3 / 9^3 grid -- refused with the library's message, and without it everything passes."""
+    C.op_conv3d_case(K, "cpu", 1, 8, 16, D, geom, need_dx=False, what="emul Conv3d")
+    conv = torch.nn.Conv3d(8, 16, geom[0], geom[1], padding=geom[2], dilation=geom[3])
+    x = torch.randn(1, D ** 3, 8).to(torch.bfloat16).requires_grad_(True)
+    out = K.conv3d(x, conv, D)
+    # (the emulated library's check names the refused call; on the GPU the validator's own text is matched)
+    with pytest.raises(RuntimeError, match=r"mf_conv3d_bf16_fwd \(data gradient\)"):
+        out.backward(torch.ones_like(out))
+
+
 @pytest.mark.parametrize("n,Kin,N,relu", [(150, 3, 8, True), (130, 64, 63, False), (200, 984, 640, True)])
 def test_linear_operator_forward_and_gradients(K, n, Kin, N, relu):
     torch.manual_seed(1)
@@ -110,6 +161,8 @@ def test_linear_operator_forward_and_gradients(K, n, Kin, N, relu):
     y.backward(g.float())
     assert out.shape == (n, N) and out.dtype == torch.bfloat16
     assert rel(out, y.detach()) < 2 ** -7
+    ref, S = BB.linear_ref(xr, wr, br)
+    BB.assert_within(out, F.relu(ref) if relu else ref, S, Kin + 1, "Linear operator fwd")
     assert rel(x.grad, xr.grad) < 2e-2
     assert rel(conv.weight.grad.reshape(N, Kin), wr.grad) < 2e-2
     assert rel(conv.bias.grad, br.grad) < 2e-2
