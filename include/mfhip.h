@@ -821,6 +821,64 @@ int mf_meshsdf_prepare(const mfMeshSdfBatch *batch, int64_t total_faces, mfStrea
 /* One lane per query over every face of its mesh; face_rec as prepared. */
 int mf_meshsdf_query(const mfMeshSdfBatch *batch, mfStream_t stream);
 
+/* ---- depth / instance rasteriser and full grids (geometry/render.py, csrc/render.hip) ----------
+ * One launch renders N items: item n = mesh item_mesh[n] at the float64 pose item_T[n] (cad -> camera,
+ * row-major 4 x 4) into image item_target[n] with the instance id item_id[n].  Items of one target
+ * occlude each other.  The arithmetic is DESIGN.md "Mesh rendering": float64 projection
+ * u = fx x / z + cx, pixel (row i, col j) sampled at (u, v) = (j, i), float64 edge functions in a canonical
+ * endpoint order with a top-left rule, both sides drawn, a face with a vertex at z <= near dropped whole,
+ * depth = the face's plane along the pixel's ray rounded once to float32, winner = the minimum of
+ * (depth bits, item, face) by a 64-bit atomic minimum: the result does not depend on the execution order.
+ * Every call is asynchronous, allocates nothing and never synchronises. */
+#define MF_RENDER_MAX_ITEMS 65535
+#define MF_RENDER_MAX_FACES (1LL << 26) /* face records (faces summed over the items) per launch */
+#define MF_RENDER_MAX_PIXELS (1LL << 28) /* n_targets * height * width */
+#define MF_RENDER_MAX_SIDE 4096          /* height, width */
+typedef struct {
+  const double *vertices;      /* packed [V, 3] */
+  const int64_t *v_off;        /* [M + 1] vertex row offsets */
+  const int32_t *faces;        /* packed [F, 3], indices local to the mesh (outside it: the face is dropped) */
+  const int64_t *f_off;        /* [M + 1] face row offsets */
+  const int32_t *item_mesh;    /* [N] */
+  const double *item_T;        /* [N, 16] */
+  const int32_t *item_target;  /* [N] in [0, n_targets) */
+  const int32_t *item_id;      /* [N] value written to `instance` */
+  const int64_t *item_rec_off; /* [N + 1] record offsets: item n owns records item_rec_off[n] + (face of its mesh) */
+  void *workspace;             /* mf_render_workspace_bytes, 16-byte aligned */
+  float *depth;                /* [n_targets, height, width], NaN where nothing was hit */
+  int32_t *instance;           /* [n_targets, height, width], -1 where nothing was hit */
+  int32_t *face;               /* [n_targets, height, width] face of the winning item's mesh, -1 where nothing */
+  int32_t *count;              /* [N] pixels each item won */
+  double fx;
+  double fy;
+  double cx;
+  double cy;
+  double near;
+  int32_t n_meshes;
+  int32_t n_items;
+  int32_t n_targets;
+  int32_t height;
+  int32_t width;
+  int32_t reserved;
+} mfRenderBatch;
+/* Host-only: bytes of the workspace (z-buffer, face records, large-face list); < 0 past a cap above. */
+int64_t mf_render_workspace_bytes(int64_t total_records, int64_t n_targets, int64_t height, int64_t width);
+/* Clears the z-buffer and writes one record per (item, face): clipped bounding box, edges, plane; faces whose
+ * box exceeds the small-face threshold are listed for the large pass.  total_records = item_rec_off[N]. */
+int mf_render_setup(const mfRenderBatch *batch, int64_t total_records, mfStream_t stream);
+/* Both raster passes: a lane per small face, a workgroup per (large face, 32 x 32 tile). */
+int mf_render_raster(const mfRenderBatch *batch, int64_t total_records, mfStream_t stream);
+/* z-buffer -> depth, instance, face and the per-item pixel counts. */
+int mf_render_resolve(const mfRenderBatch *batch, int64_t total_records, mfStream_t stream);
+/* grid_target_full / grid_nontarget_full of N examples in one launch (datasets/rgbd_pose_estimation/base.py
+ * _get_grid_full): the points of example i (points[p_off[i] .. p_off[i + 1]), float64 [*, 3]) at T[i] into the
+ * dim^3 grid of every example e: idx = rint((T_i p - origin_e) / pitch_e) kept inside [0, dim)^3;
+ * target_full[e] = 1 from i = e, nontarget_full[e] = max over i != e of (position of i among the others) + 1.
+ * Both outputs int32 [N, dim, dim, dim], cleared here; total_points = p_off[N]. */
+int mf_full_grids(const double *points, const int64_t *p_off, const double *T, const double *pitch,
+                  const double *origin, int32_t n_examples, int64_t total_points, int32_t dim,
+                  int32_t *target_full, int32_t *nontarget_full, mfStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

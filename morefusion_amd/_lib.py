@@ -61,6 +61,16 @@ class MeshSdfBatch(ctypes.Structure):
         ("n_meshes", _i), ("n_blocks", _i), ("grid_dim", _i), ("reserved", _i)]
 
 
+class RenderBatch(ctypes.Structure):
+    """mfRenderBatch (include/mfhip.h)."""
+
+    _fields_ = [(n, _p) for n in (
+        "vertices", "v_off", "faces", "f_off", "item_mesh", "item_T", "item_target", "item_id", "item_rec_off",
+        "workspace", "depth", "instance", "face", "count")] + [
+        (n, _d) for n in ("fx", "fy", "cx", "cy", "near")] + [
+        (n, _i) for n in ("n_meshes", "n_items", "n_targets", "height", "width", "reserved")]
+
+
 _SIGNATURES = {
     "mf_version": ([], _i),
     "mf_last_error_string": ([], ctypes.c_char_p),
@@ -183,6 +193,11 @@ _SIGNATURES = {
     "mf_meshsdf_workspace_bytes": ([_i64], _i64),
     "mf_meshsdf_prepare": ([ctypes.POINTER(MeshSdfBatch), _i64, _p], _i),
     "mf_meshsdf_query": ([ctypes.POINTER(MeshSdfBatch), _p], _i),
+    "mf_render_workspace_bytes": ([_i64] * 4, _i64),
+    "mf_render_setup": ([_p, _i64, _p], _i),  # (mfRenderBatch by reference: ctypes.byref(RenderBatch))
+    "mf_render_raster": ([_p, _i64, _p], _i),
+    "mf_render_resolve": ([_p, _i64, _p], _i),
+    "mf_full_grids": ([_p] * 5 + [_i, _i64, _i, _p, _p, _p], _i),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -7,3 +7,4 @@ from .pointcloud_from_depth import pointcloud_from_depth
 from .quaternion_from_matrix import quaternion_from_matrix, translation_from_matrix
 from .instance_crops import grid_origin, instance_crops
 from .mesh_sdf import load_obj, mesh_signed_distance, solid_voxel_grid
+from .render import full_grids, render_meshes

@@ -355,6 +355,53 @@ def make_occupancy_frame(seed=0, height=480, width=640, n_objects=8):
     return dict(rgb=rgb, depth=depth, K=K, label=label, instance_ids=instance_ids, class_ids=class_ids)
 
 
+def quad_mesh(p00, p10, p11, p01):
+    """Two triangles over the corners p00 -> p10 -> p11 -> p01."""
+    return np.asarray([p00, p10, p11, p01], np.float64), np.asarray([[0, 1, 2], [0, 2, 3]], np.int32)
+
+
+def make_cad_frame(meshes_by_class, seed=0, height=480, width=640, n_objects=3, device=None):
+    """A frame rendered from triangle meshes with known poses: ``n_objects`` CAD models (``meshes_by_class`` =
+    {class_id: (vertices, faces)}, classes drawn in turn from a shuffled list) standing at random orientations on a
+    table quad in front of a wall quad, drawn by ``geometry.render_meshes`` (csrc/render.hip) from a pinhole camera
+    at the origin (looking along +z, y down; the intrinsics scale with the width).  Crops, occupancy, CAD data and
+    ground truth all describe the same scene.  Labels: 0 = wall, 1 = table, instance_ids[i] = 2 + i.  Returns
+    dict(rgb u8 [H, W, 3], depth f32 [H, W] with a few NaN holes, label i32 [H, W], K [3, 3] float64, instance_ids
+    i32 [n], class_ids i32 [n], Ts_cad2cam float64 [n, 4, 4]) as NumPy."""
+    from .geometry import render_meshes
+
+    rs = np.random.RandomState(seed)
+    s = width / 640.0
+    K = np.array([[619.4 * s, 0, width / 2 - 0.3], [0, 618.9 * s, height / 2 + 0.7], [0, 0, 1]])
+    table_y, wall_z = 0.2, 1.4
+    classes = sorted(int(c) for c in meshes_by_class)
+    order = list(rs.permutation(classes))
+    class_ids = np.asarray([order[i % len(order)] for i in range(n_objects)], np.int32)
+    instance_ids = np.arange(2, 2 + n_objects, dtype=np.int32)
+    Ts = np.zeros((n_objects, 4, 4))
+    for i, c in enumerate(class_ids):
+        v = np.asarray(meshes_by_class[int(c)][0], np.float64)
+        T = np.eye(4)
+        T[:3, :3] = random_rotation(rs)
+        centre = (v.max(0) + v.min(0)) / 2
+        x = -0.3 + 0.6 * (i + rs.uniform(0.35, 0.65)) / n_objects
+        z = rs.uniform(0.65, 0.8)
+        T[:3, 3] = np.array([x, 0.0, z]) - T[:3, :3] @ centre
+        T[1, 3] += table_y - (v @ T[:3, :3].T + T[:3, 3])[:, 1].max()  # the lowest point rests on the table
+        Ts[i] = T
+    wall = quad_mesh((-3, -3, wall_z), (3, -3, wall_z), (3, 3, wall_z), (-3, 3, wall_z))
+    table = quad_mesh((-1.5, table_y, 0.2), (1.5, table_y, 0.2), (1.5, table_y, wall_z), (-1.5, table_y, wall_z))
+    meshes = [wall, table] + [meshes_by_class[int(c)] for c in class_ids]
+    out = render_meshes(meshes, np.concatenate([np.eye(4)[None], np.eye(4)[None], Ts]), K, height, width,
+                        instance_ids=[0, 1] + instance_ids.tolist(), device=device)
+    depth = out["depth"][0].cpu().numpy()
+    label = np.maximum(out["instance"][0].cpu().numpy(), 0).astype(np.int32)
+    depth[rs.uniform(size=depth.shape) < 0.03] = np.nan
+    palette = rs.randint(0, 256, (2 + n_objects, 3)).astype(np.uint8)
+    return dict(rgb=palette[label], depth=depth, label=label, K=K, instance_ids=instance_ids, class_ids=class_ids,
+                Ts_cad2cam=Ts)
+
+
 def _euler_pose(ang, t):
     T = np.eye(4)
     T[:3, :3] = random_rotation_from_euler(ang)
