@@ -334,6 +334,18 @@ int mf_sparse_conv3d_k4s2_points_cl_fwd(const float *values, int64_t ldv, const 
 int mf_interpolate_voxel_grid_cl_fwd(const float *vox, const float *points, const int32_t *batch_indices,
                                      int64_t n, int B, int C, int X, int Y, int Z, float *out, int64_t ldo,
                                      mfStream_t stream);
+/* The same two with split-bf16 outputs (operands of mf_conv3d_k4s2_split_fwd / mf_linear_split_fwd): the sparse conv3
+ * also writes out_split bf16 [B, (D/2)^3, 2 Cout] = the split of its fp32 output; the sampler writes hi at
+ * outs[p*ldos + c] and lo at outs[p*ldos + los + c] of bf16 rows INSTEAD of the fp32 samples. */
+int mf_sparse_conv3d_k4s2_points_cl_split_fwd(const float *values, int64_t ldv, const float *points,
+                                              const int32_t *batch_indices, int64_t n, float ox, float oy, float oz,
+                                              float pitch, const float *Wp, const float *dense, const float *bias,
+                                              float *out, void *out_split, void *ws, int32_t B, int32_t Cs,
+                                              int32_t Cout, int32_t D, int32_t max_rows, int32_t relu,
+                                              mfStream_t stream);
+int mf_interpolate_voxel_grid_cl_split_fwd(const float *vox, const float *points, const int32_t *batch_indices,
+                                           int64_t n, int B, int C, int X, int Y, int Z, void *outs, int64_t ldos,
+                                           int64_t los, mfStream_t stream);
 int mf_occupancy_convs_fwd(const float *grid, const float *w1, const float *b1, const float *w2,
                            const float *b2, float *h1, float *h2, int32_t B, int32_t D, mfStream_t stream);
 
@@ -434,6 +446,27 @@ int mf_conv2d_split_fwd(const void *xs, const void *wp, const float *bias, const
                         const float *slope, int32_t act, float *out32, int32_t ldo32, void *outs, int32_t ldos,
                         int32_t los, void *ws, int64_t ws_bytes, int32_t B, int32_t Cin, int32_t Cout, int32_t D,
                         int32_t ks, int32_t stride, int32_t pad, int32_t dil, mfStream_t stream);
+/* The volumetric part's fp32 layers on the same scheme (fp32 inference; the fp32-MFMA entries mf_conv3d_k4s2_fwd /
+ * mf_linear_fwd are unchanged and serve small batches).  Outputs as mf_conv2d_split_fwd: v = act(.. + bias), relu 0 / 1,
+ * out32[m * ldo32 + n] = v and / or outs[m * ldos + n] = hi(v), outs[m * ldos + los + n] = lo(v).  ws: the matching
+ * *_workspace_bytes(...) bytes of split-K slabs (0: none needed); slabs are added in slab order (bit-reproducible).
+ * mf_conv3d_k4s2_split_pack  W fp32 [Cout][w_cin][4][4][4], channels c_off .. c_off + Cin - 1 -> wp bf16 [Cout][64][3 Cin]
+ * mf_conv3d_k4s2_split_fwd   Convolution3D k4 s2 p1: xs bf16 [B][D^3][2 Cin] (hi channels, then lo channels), row m =
+ *                            (b, output voxel), D / 2 a power of two
+ * mf_linear_split_pack       W fp32 [G][N][K] (row pitch ldw, group stride w_gs) -> wp bf16 [G][Np][3 Kp], zero padded
+ * mf_linear_split_fwd        As bf16 [M][lda]: columns 0 .. Kp - 1 hi, Kp .. 2 Kp - 1 lo; wp [Np >= N][3 Kp]; N % 8 == 0 */
+int mf_conv3d_k4s2_split_pack(const float *W, int32_t Cout, int32_t Cin, int32_t w_cin, int32_t c_off, void *wp,
+                              mfStream_t stream);
+int64_t mf_conv3d_k4s2_split_workspace_bytes(int32_t B, int32_t Cin, int32_t Cout, int32_t D);
+int mf_conv3d_k4s2_split_fwd(const void *xs, const void *wp, const float *bias, int32_t relu, float *out32,
+                             int32_t ldo32, void *outs, int32_t ldos, int32_t los, void *ws, int64_t ws_bytes, int32_t B,
+                             int32_t Cin, int32_t Cout, int32_t D, mfStream_t stream);
+int mf_linear_split_pack(const float *W, int64_t w_gs, int32_t ldw, int32_t N, int32_t K, int32_t Np, int32_t Kp,
+                         int32_t groups, void *wp, mfStream_t stream);
+int64_t mf_linear_split_workspace_bytes(int64_t M, int32_t N, int32_t Kp);
+int mf_linear_split_fwd(const void *As, int32_t lda, const void *wp, const float *bias, int32_t relu, float *out32,
+                        int32_t ldo32, void *outs, int32_t ldos, int32_t los, void *ws, int64_t ws_bytes, int32_t M,
+                        int32_t N, int32_t Kp, mfStream_t stream);
 /* 3 x 3 x 3, stride 1, pad = dilation convolutions between NARROW layers (read channels 8 or 16, written channels <= 16)
  * on channels-last bf16 grids -- the occupancy branch conv1_occ / conv2_occ (model.py:69-72,120-124) and conv2_occ's
  * data gradient (pack with transpose = 1): voxels are the MFMA's columns, operands straight from global memory.

@@ -128,6 +128,14 @@ _SIGNATURES = {
     "mf_conv2d_split_pack": ([_p] + [_i] * 3 + [_p, _p], _i),
     "mf_conv2d_split_workspace_bytes": ([_i] * 8, _i64),
     "mf_conv2d_split_fwd": ([_p, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _i, _p, _i64] + [_i] * 8 + [_p], _i),
+    "mf_conv3d_k4s2_split_pack": ([_p] + [_i] * 4 + [_p, _p], _i),
+    "mf_conv3d_k4s2_split_workspace_bytes": ([_i] * 4, _i64),
+    "mf_conv3d_k4s2_split_fwd": ([_p, _p, _p, _i, _p, _i, _p, _i, _i, _p, _i64] + [_i] * 4 + [_p], _i),
+    "mf_linear_split_pack": ([_p, _i64] + [_i] * 6 + [_p, _p], _i),
+    "mf_linear_split_workspace_bytes": ([_i64, _i, _i], _i64),
+    "mf_linear_split_fwd": ([_p, _i, _p, _p, _i, _p, _i, _p, _i, _i, _p, _i64] + [_i] * 3 + [_p], _i),
+    "mf_sparse_conv3d_k4s2_points_cl_split_fwd": ([_p, _i64, _p, _p, _i64, _f, _f, _f, _f, _p, _p, _p, _p, _p, _p] + [_i] * 6 + [_p], _i),
+    "mf_interpolate_voxel_grid_cl_split_fwd": ([_p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _i64, _i64, _p], _i),
     "mf_conv3d_k3_narrow_bf16_pack_elems": ([_i], _i64),
     "mf_conv3d_k3_narrow_bf16_pack": ([_p] + [_i] * 5 + [_p, _p], _i),
     "mf_conv3d_k3_narrow_bf16": ([_p, _p, _p, _p] + [_i] * 6 + [_p], _i),

@@ -95,9 +95,11 @@ class SparseVoxelConv3d:
         return out
 
     @torch.no_grad()
-    def from_points_cl(self, values, ldv, points, batch_indices, batch_size, dense_cl=None, dim=32, relu=True):
+    def from_points_cl(self, values, ldv, points, batch_indices, batch_size, dense_cl=None, dim=32, relu=True,
+                       out_split=None):
         """Channels-last form of ``from_points``: ``values`` is an [n, Cs] column block of a wider row-major
-        matrix (row pitch ``ldv`` floats), ``dense_cl`` / the result are [B, (D/2)^3, Cout]."""
+        matrix (row pitch ``ldv`` floats), ``dense_cl`` / the result are [B, (D/2)^3, Cout].  ``out_split`` (bf16
+        [B, (D/2)^3, 2 Cout]) also receives the split-bf16 form of the result (hi channels, then lo channels)."""
         _lib.require_gpu(values, points, batch_indices)
         n, Cs = values.shape
         B, D = int(batch_size), int(dim)
@@ -114,6 +116,15 @@ class SparseVoxelConv3d:
         pts, bi = _lib.f32c(points), _lib.i32c(batch_indices)
         out = torch.empty((B, (D // 2) ** 3, Cout), dtype=torch.float32, device=values.device)
         bias = self.conv.bias.detach().float().contiguous() if self.conv.bias is not None else None
+        if out_split is not None:
+            if out_split.dtype != torch.bfloat16 or out_split.numel() != 2 * out.numel() or not out_split.is_contiguous():
+                raise TypeError("out_split must be a contiguous bfloat16 [B, (D/2)^3, 2 Cout]")
+            _lib.check(lib.mf_sparse_conv3d_k4s2_points_cl_split_fwd(
+                values.data_ptr(), int(ldv), pts.data_ptr(), bi.data_ptr(), n, 0.0, 0.0, 0.0, 1.0,
+                self.Wp.data_ptr(), _lib.ptr(dense_cl), _lib.ptr(bias), out.data_ptr(), out_split.data_ptr(),
+                self._ws.data_ptr(), B, Cs, Cout, D, max_rows, int(relu), _lib.stream_ptr()),
+                "mf_sparse_conv3d_k4s2_points_cl_split_fwd")
+            return out
         _lib.check(lib.mf_sparse_conv3d_k4s2_points_cl_fwd(
             values.data_ptr(), int(ldv), pts.data_ptr(), bi.data_ptr(), n, 0.0, 0.0, 0.0, 1.0,
             self.Wp.data_ptr(), _lib.ptr(dense_cl), _lib.ptr(bias), out.data_ptr(), self._ws.data_ptr(),

@@ -15,6 +15,12 @@ per-point heads) for ``torch.no_grad()`` on the MI355X with every 3-D operator h
                      heads as ONE [n, 984] x [984, 1920] GEMM, layers 2-4 with the heads side by side, each
                      reading / writing its column block (under bf16 autocast: stock ``F.linear``)
 
+From ``SPLIT_MIN_BATCH`` objects on (fp32 inference, ``split_bf16``), conv4 and the heads' first layer run as
+split-bf16 GEMMs on the bf16 MFMA instead (mf_conv3d_k4s2_split_fwd / mf_linear_split_fwd): sparse
+conv3's reduce writes the split form of h3 beside the fp32 grid, the samplers write their columns of the heads'
+input straight into its split form Fs [n, 2 x 992] (hi columns, then lo columns), the point-MLP columns are split
+by one mf_split_bf16 call.
+
 Grids are [B, D^3, C] (a voxel's channels are contiguous: the implicit GEMM's K runs over
 (tap, channel) without gathers, and a trilinear corner is one coalesced row read); nothing is
 transposed between the stages and ``torch.cat`` of the four feature groups never happens.
@@ -33,9 +39,16 @@ from .sparse_conv import SparseVoxelConv3d
 # lines: every chunk straddled two).  Columns 984..991 are zero (and so are the packed weights' columns there).
 F_COLS, F_LD = 984, 992
 
+# Smallest batch (objects) from which a layer takes the split-bf16 path; below it the fp32-MFMA kernels run as before
+# (tools/time_volumetric_split.py, profiles/volumetric_split_bf16_layers.csv: at one object conv4 has 4 output tiles of
+# 256 x 256 for 256 CUs).  Static, like backbone2d.SPLIT_MIN_BATCH.
+SPLIT_MIN_BATCH = {"conv4": 4, "heads1": 4}
+
 
 class ChannelsLastVolumetric:
     """Weight packs, workspaces and the launch sequence; one instance per Model (and device)."""
+
+    split_bf16 = True  # conv4 and heads layer 1 as split-bf16 GEMMs in fp32 inference (class switch: A/B without rebuild)
 
     def __init__(self, model):
         self.m = model
@@ -80,13 +93,14 @@ class ChannelsLastVolumetric:
         return self._pack(name, [conv.weight, conv.bias],
                           lambda: (conv.weight.detach().squeeze(-1).contiguous(), conv.bias.detach()))
 
-    def _scratch(self, name, shape, device, dtype=torch.float32):
+    def _scratch(self, name, shape, device, dtype=torch.float32, zero=False):
         """Reusable intermediate of one shape.  Keyed by (name, shape): a buffer is never replaced or freed once
-        handed out, because a captured hipGraph (predict_graphed) of another batch size keeps its address."""
+        handed out, because a captured hipGraph (predict_graphed) of another batch size keeps its address.
+        ``zero``: filled with zeros when it is created (padding columns nobody writes afterwards)."""
         key = (name, tuple(shape), str(device), dtype)
         t = self._buf.get(key)
         if t is None:
-            t = torch.empty(shape, dtype=dtype, device=device)
+            t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=device)
             self._buf[key] = t
         return t
 
@@ -105,6 +119,67 @@ class ChannelsLastVolumetric:
                                         out.data_ptr(), ws.data_ptr(), B, cin, cout, D, int(split), int(relu),
                                         _lib.stream_ptr()), "mf_conv3d_k4s2_fwd")
         return out
+
+    # ---- the split-bf16 path ------------------------------------------------------
+    def _split_path(self, layer, B):
+        """fp32 inference on the MFMA path with at least SPLIT_MIN_BATCH[layer] objects."""
+        return (self.split_bf16 and self.mfma_linear and not torch.is_autocast_enabled()
+                and not torch.is_grad_enabled() and B >= SPLIT_MIN_BATCH[layer])
+
+    def conv_k4s2_split(self, name, conv, xs_cl, B, D, cin, c_off=0, relu=True, bias=True, out_split=None):
+        """xs_cl bf16 [B, D^3, 2 cin] (hi | lo) -> fp32 [B, (D/2)^3, Cout] through the split-bf16 implicit GEMM
+        (and its split form into ``out_split`` [B, (D/2)^3, 2 Cout] when given)."""
+        L = _lib.lib()
+
+        def build():
+            w = conv.weight.detach().float().contiguous()
+            wp = torch.empty((w.shape[0], 64, 3 * cin), dtype=torch.bfloat16, device=w.device)
+            _lib.check(L.mf_conv3d_k4s2_split_pack(w.data_ptr(), w.shape[0], cin, w.shape[1], c_off, wp.data_ptr(),
+                                                   _lib.stream_ptr()), "mf_conv3d_k4s2_split_pack")
+            return wp, (conv.bias.detach().float().contiguous() if conv.bias is not None else None)
+        wp, b = self._pack(name + "_split", [conv.weight] + ([conv.bias] if conv.bias is not None else []), build)
+        cout = wp.shape[0]
+        nbytes = L.mf_conv3d_k4s2_split_workspace_bytes(B, cin, cout, D)
+        ws = self._scratch(name + "_split_ws", (max(nbytes, 16),), xs_cl.device, torch.uint8)
+        out = torch.empty((B, (D // 2) ** 3, cout), dtype=torch.float32, device=xs_cl.device)
+        _lib.check(L.mf_conv3d_k4s2_split_fwd(xs_cl.data_ptr(), wp.data_ptr(), _lib.ptr(b if bias else None), int(relu),
+                                              out.data_ptr(), cout, _lib.ptr(out_split), 2 * cout, cout, ws.data_ptr(),
+                                              nbytes, B, cin, cout, D, _lib.stream_ptr()), "mf_conv3d_k4s2_split_fwd")
+        return out
+
+    def sample_split(self, vox_cl, D, pts, batch_indices, fs_block, ldos, los):
+        """``sample`` with the samples written in split form: hi at ``fs_block`` (a column view of Fs), lo ``los``
+        columns further."""
+        B, _, C = vox_cl.shape
+        _lib.check(_lib.lib().mf_interpolate_voxel_grid_cl_split_fwd(
+            vox_cl.data_ptr(), pts.data_ptr(), batch_indices.data_ptr(), pts.shape[0], B, C, D, D, D,
+            fs_block.data_ptr(), ldos, los, _lib.stream_ptr()), "mf_interpolate_voxel_grid_cl_split_fwd")
+
+    def _split_cols(self, feat, c0, c1, fs):
+        """Columns c0 .. c1 - 1 of the fp32 rows ``feat`` -> their split form in Fs (one mf_split_bf16 launch)."""
+        n = feat.shape[0]
+        _lib.check(_lib.lib().mf_split_bf16(feat[:, c0:].data_ptr(), 0, 1, 0, feat.stride(0), 1, c1 - c0, 1, n,
+                                            fs[:, c0:].data_ptr(), 2 * F_LD, F_LD, _lib.stream_ptr()), "mf_split_bf16")
+
+    def heads1_split(self, fs, h1):
+        """Layer 1 of the three heads on the split form Fs [n, 2 x 992] -> h1 fp32 [n, 1920] (bias + ReLU)."""
+        m, L = self.m, _lib.lib()
+        names = ("rot", "trans", "conf")
+
+        def build():
+            w = torch.cat([getattr(m, f"conv1_{k}").weight.detach().float().squeeze(-1) for k in names]).contiguous()
+            wp = torch.empty((w.shape[0], 3 * F_LD), dtype=torch.bfloat16, device=w.device)
+            _lib.check(L.mf_linear_split_pack(w.data_ptr(), 0, w.shape[1], w.shape[0], w.shape[1], w.shape[0], F_LD, 1,
+                                              wp.data_ptr(), _lib.stream_ptr()), "mf_linear_split_pack")
+            return wp, torch.cat([getattr(m, f"conv1_{k}").bias.detach().float() for k in names]).contiguous()
+        wp, b = self._pack("gemm_heads1_split", [t for k in names for t in (getattr(m, f"conv1_{k}").weight,
+                                                                             getattr(m, f"conv1_{k}").bias)], build)
+        n, N = fs.shape[0], wp.shape[0]
+        nbytes = L.mf_linear_split_workspace_bytes(n, N, F_LD)
+        ws = self._scratch("heads1_split_ws", (max(nbytes, 16),), fs.device, torch.uint8)
+        _lib.check(L.mf_linear_split_fwd(fs.data_ptr(), 2 * F_LD, wp.data_ptr(), b.data_ptr(), 1, h1.data_ptr(),
+                                         h1.stride(0), None, 0, 0, ws.data_ptr(), nbytes, n, N, F_LD,
+                                         _lib.stream_ptr()), "mf_linear_split_fwd")
 
     def occupancy(self, grid):
         """grid_nontarget_empty [B, D, D, D] -> relu(conv2_occ(relu(conv1_occ))) as [B, D^3, 16]."""
@@ -157,6 +232,9 @@ class ChannelsLastVolumetric:
         to_center = tc4[:, :3]
         feat = torch.empty((n, F_LD), dtype=torch.float32, device=dev)
         feat[:, F_COLS:].zero_()
+        split4, split1 = self._split_path("conv4", B), self._split_path("heads1", B)
+        # Fs: the split form of F (padding columns zero from its creation on: nobody writes them)
+        fs = self._scratch("feat_split", (n, 2 * F_LD), dev, torch.bfloat16, zero=True) if split1 else None
 
         if self.mfma_linear and not torch.is_autocast_enabled():
             self._linear("conv1_rgb", [m.conv1_rgb], x_rgb, 32, feat[:, 0:64], F_LD, relu=True)
@@ -180,11 +258,21 @@ class ChannelsLastVolumetric:
         if m._with_occupancy:
             h_occ = self.occupancy(grid_nontarget_empty)
             dense = self.conv_k4s2("conv3_occ", m.conv3, h_occ, B, D, cin=16, c_off=144, relu=False, bias=False)
-        h3 = self._sparse.from_points_cl(feat[:, 72:216], F_LD, pts, batch_indices, B, dense, D)  # [B, 16^3, 256]
+        h3s = self._scratch("h3_split", (B, (D // 2) ** 3, 2 * m.conv3.out_channels), dev, torch.bfloat16) if split4 else None
+        h3 = self._sparse.from_points_cl(feat[:, 72:216], F_LD, pts, batch_indices, B, dense, D, out_split=h3s)  # [B, 16^3, 256]
         pts2 = pts * 0.5  # == pts / 2.0 (a power of two: same bits); one launch serves both samplers' scales
-        self.sample(h3, D // 2, pts2, batch_indices, feat[:, 216:472], F_LD)
-        h4 = self.conv_k4s2("conv4", m.conv4, h3, B, D // 2, cin=256)                            # [B, 8^3, 512]
-        self.sample(h4, D // 4, pts2 * 0.5, batch_indices, feat[:, 472:984], F_LD)
+        if split4:
+            h4 = self.conv_k4s2_split("conv4", m.conv4, h3s, B, D // 2, cin=256)                 # [B, 8^3, 512]
+        else:
+            h4 = self.conv_k4s2("conv4", m.conv4, h3, B, D // 2, cin=256)
+        if split1:   # the samplers' columns exist in split form only; ``heads`` finds Fs on the returned tensor
+            self._split_cols(feat, 0, 216, fs)
+            self.sample_split(h3, D // 2, pts2, batch_indices, fs[:, 216:], 2 * F_LD, F_LD)
+            self.sample_split(h4, D // 4, pts2 * 0.5, batch_indices, fs[:, 472:], 2 * F_LD, F_LD)
+            feat._mf_split = fs
+        else:
+            self.sample(h3, D // 2, pts2, batch_indices, feat[:, 216:472], F_LD)
+            self.sample(h4, D // 4, pts2 * 0.5, batch_indices, feat[:, 472:984], F_LD)
         return feat, pts
 
     # ---- 1x1 convolutions as grouped fp32-MFMA GEMMs -------------------------------------------
@@ -241,9 +329,16 @@ class ChannelsLastVolumetric:
             o = torch.empty((n, 3 * np4), dtype=torch.float32, device=dev)
             L = _lib.lib()
             assert feat.stride(0) == F_LD
-            _lib.check(L.mf_linear_fwd(feat.data_ptr(), 0, F_LD, w1.data_ptr(), 0, F_LD, b1.data_ptr(), 0,
-                                       h1.data_ptr(), 0, 1920, n, 1920, 1920, F_LD, 1, 1, _lib.stream_ptr()),
-                       "mf_linear_fwd")
+            fs = getattr(feat, "_mf_split", None)   # set by ``features`` when it wrote the split form
+            if fs is None and self._split_path("heads1", B):
+                fs = self._scratch("feat_split", (n, 2 * F_LD), dev, torch.bfloat16, zero=True)
+                self._split_cols(feat, 0, F_COLS, fs)
+            if fs is not None:
+                self.heads1_split(fs, h1)
+            else:
+                _lib.check(L.mf_linear_fwd(feat.data_ptr(), 0, F_LD, w1.data_ptr(), 0, F_LD, b1.data_ptr(), 0,
+                                           h1.data_ptr(), 0, 1920, n, 1920, 1920, F_LD, 1, 1, _lib.stream_ptr()),
+                           "mf_linear_fwd")
             self._linear("heads2", [getattr(m, f"conv2_{k}") for k in names], h1, 1920, h2, 768, True, a_gs=640, o_gs=256)
             self._linear("heads3", [getattr(m, f"conv3_{k}") for k in names], h2, 768, h3, 384, True, a_gs=256, o_gs=128)
             # layer 4: N = n_fg * {4, 3, 1} -> pad every head to the widest (equal shapes per launch)

@@ -42,7 +42,12 @@ template <int MI> constexpr int nt_lds() {
   return 2 * nt_buf_bytes<MI>() > 64 * MI * (kBN + 4) * 4 ? 2 * nt_buf_bytes<MI>() : 64 * MI * (kBN + 4) * 4;
 }
 
-enum { kRows = 0, kConvFwd = 1, kConvDgrad = 2, kConv2Fwd = 3 };
+enum { kRows = 0, kConvFwd = 1, kConvDgrad = 2, kConv2Fwd = 3, kConvFwdS = 4, kRowsS = 5 };
+// kConvFwdS / kRowsS: the 3-D convolution and the rows loader on SPLIT operands (see NtArgs::xc): same addressing as
+// their plain forms but for the source-channel wrap, and the kConv2Fwd epilogue (conv2_store8).
+constexpr bool nt_conv3(int mode) { return mode == kConvFwd || mode == kConvFwdS; }
+constexpr bool nt_rows(int mode) { return mode == kRows || mode == kRowsS; }
+constexpr bool nt_split(int mode) { return mode == kConv2Fwd || mode == kConvFwdS || mode == kRowsS; }
 
 struct NtArgs {
   const uint16_t *A;   // bf16 operand (rows / channels-last grid / channels-last output gradient)
@@ -68,6 +73,8 @@ struct NtArgs {
   // [hi | lo | hi] against the packed weights [w_hi | w_hi | w_lo]).  Epilogue (conv2_store8):
   //   v = act(acc + bias[n] + res[m][n])   act: 0 none, 1 ReLU, 2 PReLU with the single slope *slope
   //   out32[m][n] = v (pitch ldo32), outs[m][n] = bf16(v), outs[m][los + n] = bf16(v - bf16(v)) (pitch ldos)
+  // kConvFwdS (mf_conv3d_k4s2_split_fwd): the same for a grid [B][D^3][xc]; kRowsS (mf_linear_split_fwd): A rows
+  // [hi | lo] of xc = 2 Kp columns at pitch lda, K = 3 Kp, chunk k reads column k mod xc.  Both: groups = 1.
   int xc, act, ldr, ldo32, ldos, los;
   const float *res, *slope;
   float *out32;
@@ -155,7 +162,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
     const bool row_ok = m < a.M;
     const int mm = row_ok ? m : 0;
     int mk = row_ok ? 1 << 12 : 0;
-    if (MODE == kRows) {
+    if (nt_rows(MODE)) {
       base[i] = mm * a.lda;
     } else if (MODE == kConv2Fwd) {  // row m = (b, oy, ox); bits ky | 4 + kx = tap row / column inside the map
       const int b = mm >> (2 * dol), o = mm & ((1 << (2 * dol)) - 1);
@@ -166,11 +173,11 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
         mk |= ((unsigned)(y0 + a.dil * k) < (unsigned)a.D ? 1 : 0) << k;
         mk |= ((unsigned)(x0 + a.dil * k) < (unsigned)a.D ? 1 : 0) << (4 + k);
       }
-    } else if (MODE == kConvFwd) {
+    } else if (nt_conv3(MODE)) {
       const int b = mm >> (3 * dol), o = mm & ((1 << (3 * dol)) - 1);
       const int ox = o >> (2 * dol), oy = (o >> dol) & (Do - 1), oz = o & (Do - 1);
       const int x0 = a.stride * ox - a.pad, y0 = a.stride * oy - a.pad, z0 = a.stride * oz - a.pad;
-      base[i] = (((b * a.D + x0) * a.D + y0) * a.D + z0) * a.Cin;
+      base[i] = (((b * a.D + x0) * a.D + y0) * a.D + z0) * (MODE == kConvFwdS ? a.xc : a.Cin);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {  // (k >= ks: never asked for)
         mk |= ((unsigned)(x0 + a.dil * k) < (unsigned)a.D ? 1 : 0) << k;
@@ -220,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
   // two integer divisions per fetch and 64-bit address arithmetic per load, 12 VALU instructions per MFMA by
   // SQ_INSTS_VALU; the MFMA pipe at 0.37).
   int kg = 8 * chunk, tc = 0, tx = 0, ty = 0, tz = 0;  // conv fwd: tap (tx, ty, tz), channel tc; dgrad: slot tx, cout tc
-  if (MODE == kConvFwd) {
+  if (nt_conv3(MODE)) {
     const int tap = kg / a.Cin;
     tc = kg - tap * a.Cin;
     const int kxy = tap / a.ks;
@@ -246,9 +253,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
   {                                                                                                   \
     const bool kin_ = kg + 8 <= a.K;                                                                  \
     const uint32_t kofs_ = kin_ ? 2u * (uint32_t)kg : 0u;                                             \
-    int off_ = kg, bits_ = 1 << 12;                                                                   \
-    if (MODE == kConvFwd) {                                                                           \
-      off_ = ((tx * a.D + ty) * a.D + tz) * a.dil * a.Cin + tc;                                       \
+    int off_ = MODE == kRowsS && kg >= a.xc ? kg - a.xc : kg, bits_ = 1 << 12;                        \
+    if (nt_conv3(MODE)) {                                                                             \
+      off_ = ((tx * a.D + ty) * a.D + tz) * a.dil * (MODE == kConvFwdS ? a.xc : a.Cin) +              \
+             (MODE == kConvFwdS && tc >= a.xc ? tc - a.xc : tc);                                      \
       bits_ = tx < a.ks ? (1 << tx) | (16 << ty) | (256 << tz) | (1 << 12) : 1 << 13;                 \
     } else if (MODE == kConv2Fwd) {                                                                   \
       off_ = (tx * a.D + ty) * a.dil * a.xc + (tc >= a.xc ? tc - a.xc : tc);                          \
@@ -263,7 +271,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
     if constexpr (MI == 2) { MF_NT_LOAD_A(S, 2 * MI - 2, ra2##S) MF_NT_LOAD_A(S, 2 * MI - 1, ra3##S) } \
     MF_NT_LOAD_B(S, 0, rb0##S) MF_NT_LOAD_B(S, 1, rb1##S) MF_NT_LOAD_B(S, 2, rb2##S) MF_NT_LOAD_B(S, 3, rb3##S) \
     kg += kBK;                                                                                        \
-    if (MODE == kConvFwd) {                                                                           \
+    if (nt_conv3(MODE)) {                                                                             \
       tc += kBK;                                                                                      \
       while (tc >= a.Cin) {                                                                           \
         tc -= a.Cin;                                                                                  \
@@ -376,7 +384,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
   // epilogue through LDS (the loop ended on a barrier: the operand buffers are free)
   constexpr int kEp = kBN + 4;
   float *s_out = reinterpret_cast<float *>(s_raw);  // [kBM][kEp]
-  const float *bias = a.bias && MODE != kConv2Fwd ? a.bias + grp * a.b_gs : nullptr;  // (conv2: conv2_store8)
+  const float *bias = a.bias && !nt_split(MODE) ? a.bias + grp * a.b_gs : nullptr;  // (conv2: conv2_store8)
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -387,7 +395,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
       for (int e = 0; e < 16; ++e) {
         const int ml = wm * 32 * MI + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * lhalf;
         float v = acc[mi][ni][e] + bn;
-        if (a.relu && MODE != kConv2Fwd) v = v > 0.0f ? v : 0.0f;
+        if (a.relu && !nt_split(MODE)) v = v > 0.0f ? v : 0.0f;
         s_out[ml * kEp + nl] = v;
       }
     }
@@ -406,7 +414,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_bf16(NtArgs a) {
     const float4 v0 = *reinterpret_cast<const float4 *>(s_out + ml * kEp + 8 * c8);
     const float4 v1 = *reinterpret_cast<const float4 *>(s_out + ml * kEp + 8 * c8 + 4);
     float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    if (MODE == kConv2Fwd) {
+    if (nt_split(MODE)) {
       conv2_store8(a, m, n, v);
       continue;
     }
@@ -520,7 +528,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_bf16_pp(NtArgs a) {
     const bool row_ok = m < a.M;
     const int mm = row_ok ? m : 0;
     int mk = row_ok ? 1 << 12 : 0;
-    if (MODE == kRows) {
+    if (nt_rows(MODE)) {
       base[i] = mm * a.lda;
     } else if (MODE == kConv2Fwd) {  // row m = (b, oy, ox); bits ky | 4 + kx = tap row / column inside the map
       const int b = mm >> (2 * dol), o = mm & ((1 << (2 * dol)) - 1);
@@ -531,11 +539,11 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_bf16_pp(NtArgs a) {
         mk |= ((unsigned)(y0 + a.dil * k) < (unsigned)a.D ? 1 : 0) << k;
         mk |= ((unsigned)(x0 + a.dil * k) < (unsigned)a.D ? 1 : 0) << (4 + k);
       }
-    } else if (MODE == kConvFwd) {
+    } else if (nt_conv3(MODE)) {
       const int b = mm >> (3 * dol), o = mm & ((1 << (3 * dol)) - 1);
       const int ox = o >> (2 * dol), oy = (o >> dol) & (Do - 1), oz = o & (Do - 1);
       const int x0 = a.stride * ox - a.pad, y0 = a.stride * oy - a.pad, z0 = a.stride * oz - a.pad;
-      base[i] = (((b * a.D + x0) * a.D + y0) * a.D + z0) * a.Cin;
+      base[i] = (((b * a.D + x0) * a.D + y0) * a.D + z0) * (MODE == kConvFwdS ? a.xc : a.Cin);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {  // (k >= ks: never asked for)
         mk |= ((unsigned)(x0 + a.dil * k) < (unsigned)a.D ? 1 : 0) << k;
@@ -574,7 +582,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_bf16_pp(NtArgs a) {
   // this lane's position in K, advanced by one K-tile per request (see k_gemm_nt_bf16); the A requests run one tile
   // ahead of the W requests
   int kg = 8 * chunk + kBK * t0, tc = 0, tx = 0, ty = 0, tz = 0, kgw = kg;
-  if (MODE == kConvFwd) {
+  if (nt_conv3(MODE)) {
     const int tap = kg / a.Cin;
     tc = kg - tap * a.Cin;
     const int kxy = tap / a.ks;
@@ -594,9 +602,10 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_bf16_pp(NtArgs a) {
 #define MF_PP_REQ_A(sa_, i0_, i1_)                                                                    \
   {                                                                                                   \
     const bool kin_ = kg + 8 <= a.K;                                                                  \
-    int off_ = kg, bits_ = 1 << 12;                                                                   \
-    if (MODE == kConvFwd) {                                                                           \
-      off_ = ((tx * a.D + ty) * a.D + tz) * a.dil * a.Cin + tc;                                       \
+    int off_ = MODE == kRowsS && kg >= a.xc ? kg - a.xc : kg, bits_ = 1 << 12;                        \
+    if (nt_conv3(MODE)) {                                                                             \
+      off_ = ((tx * a.D + ty) * a.D + tz) * a.dil * (MODE == kConvFwdS ? a.xc : a.Cin) +              \
+             (MODE == kConvFwdS && tc >= a.xc ? tc - a.xc : tc);                                      \
       bits_ = tx < a.ks ? (1 << tx) | (16 << ty) | (256 << tz) | (1 << 12) : 1 << 13;                 \
     } else if (MODE == kConv2Fwd) {                                                                   \
       off_ = (tx * a.D + ty) * a.dil * a.xc + (tc >= a.xc ? tc - a.xc : tc);                          \
@@ -612,7 +621,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_bf16_pp(NtArgs a) {
                  dma0 + (sa_) * kPpOp + i * 64 * 128);                                                \
     if ((i1_) == 4) {                                                                                 \
       kg += kBK;                                                                                      \
-      if (MODE == kConvFwd) {                                                                         \
+      if (nt_conv3(MODE)) {                                                                           \
         tc += kBK;                                                                                    \
         while (tc >= a.Cin) {                                                                         \
           tc -= a.Cin;                                                                                \
@@ -733,8 +742,8 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_bf16_pp(NtArgs a) {
   // epilogue through LDS in four passes of 64 rows (64 x 260 floats)
   constexpr int kEp = kBNb + 4;
   float *s_out = reinterpret_cast<float *>(s_raw);  // [64][kEp]
-  const float *bias = a.bias && a.S == 1 && MODE != kConv2Fwd ? a.bias + grp * a.b_gs : nullptr;  // (conv2: conv2_store8)
-  const bool relu = a.relu && a.S == 1 && MODE != kConv2Fwd, out_f32 = a.out_f32 || a.S > 1;
+  const float *bias = a.bias && a.S == 1 && !nt_split(MODE) ? a.bias + grp * a.b_gs : nullptr;  // (conv2: conv2_store8)
+  const bool relu = a.relu && a.S == 1 && !nt_split(MODE), out_f32 = a.out_f32 || a.S > 1;
   const int ldo = a.S > 1 ? a.N : a.ldo;
   void *const outp = a.S > 1 ? (void *)(a.slab + (int64_t)split * a.M * a.N) : a.out;
 #pragma unroll
@@ -771,7 +780,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_nt_bf16_pp(NtArgs a) {
       const float4 v0 = *reinterpret_cast<const float4 *>(s_out + ml * kEp + 8 * c8);
       const float4 v1 = *reinterpret_cast<const float4 *>(s_out + ml * kEp + 8 * c8 + 4);
       float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-      if (MODE == kConv2Fwd && a.S == 1) {
+      if (nt_split(MODE) && a.S == 1) {
         conv2_store8(a, m, n, v);
         continue;
       }
@@ -1502,10 +1511,11 @@ __global__ __launch_bounds__(256) void k_splitk_finish_conv2(NtArgs a) {
   conv2_store8(a, m, n, v);
 }
 
-// W [Cout][Cin][ks][ks] fp32 (framework layout) -> wp bf16 [Cout][tap][3 Cin] = [w_hi | w_hi | w_lo] per tap, the
-// operand of the 2-D split-bf16 convolution (w_hi = bf16(w), w_lo = bf16(w - w_hi)).
-__global__ __launch_bounds__(256) void k_conv2_pack_split(const float *__restrict__ W, int Cout, int Cin, int taps,
-                                                          uint16_t *__restrict__ wp) {
+// W [Cout][w_cin][taps] fp32 (framework layout: [ks][ks] or [ks][ks][ks] taps), input channels c_off .. c_off + Cin - 1
+// -> wp bf16 [Cout][tap][3 Cin] = [w_hi | w_hi | w_lo] per tap, the operand of the split-bf16 convolutions
+// (w_hi = bf16(w), w_lo = bf16(w - w_hi)).
+__global__ __launch_bounds__(256) void k_conv2_pack_split(const float *__restrict__ W, int Cout, int Cin, int w_cin,
+                                                          int c_off, int taps, uint16_t *__restrict__ wp) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int K3 = 3 * Cin;
   if (i >= (int64_t)Cout * taps * K3) return;
@@ -1513,7 +1523,23 @@ __global__ __launch_bounds__(256) void k_conv2_pack_split(const float *__restric
   const int64_t r = i / K3;
   const int tap = (int)(r % taps), n = (int)(r / taps);
   const int seg = j / Cin, c = j - seg * Cin;
-  const float w = W[((int64_t)n * Cin + c) * taps + tap];
+  const float w = W[((int64_t)n * w_cin + c_off + c) * taps + tap];
+  const uint32_t hb = mf::bf16_bits(w);
+  wp[i] = (uint16_t)(seg < 2 ? hb : mf::bf16_bits(w - mf::bf16_lo(hb)));
+}
+
+// W [G][N][K] fp32 (row pitch ldw, group stride w_gs) -> wp bf16 [G][Np][3 Kp] = [w_hi | w_hi | w_lo] per row, zero
+// rows N .. Np - 1 and zero columns K .. Kp - 1 of every segment: the operand of mf_linear_split_fwd.
+__global__ __launch_bounds__(256) void k_rows_pack_split(const float *__restrict__ W, int64_t w_gs, int ldw, int N, int K,
+                                                         int Np, int Kp, int G, uint16_t *__restrict__ wp) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int K3 = 3 * Kp;
+  if (i >= (int64_t)G * Np * K3) return;
+  const int j = (int)(i % K3);
+  const int64_t r = i / K3;
+  const int n = (int)(r % Np), g = (int)(r / Np);
+  const int seg = j / Kp, k = j - seg * Kp;
+  const float w = n < N && k < K ? W[g * w_gs + (int64_t)n * ldw + k] : 0.0f;
   const uint32_t hb = mf::bf16_bits(w);
   wp[i] = (uint16_t)(seg < 2 ? hb : mf::bf16_bits(w - mf::bf16_lo(hb)));
 }
@@ -1645,7 +1671,7 @@ int launch_nt(const NtArgs &a, hipStream_t stream) {
     if (b.S < 1) b.S = 1;
     if (int e = mf::allow_big_lds((const void *)k_gemm_nt_bf16_pp<MODE>, nt_pp_lds())) return e;
     hipLaunchKernelGGL((k_gemm_nt_bf16_pp<MODE>), dim3((unsigned)(big * b.S)), dim3(512), nt_pp_lds(), stream, b);
-    if (b.S > 1 && MODE == kConv2Fwd)
+    if (b.S > 1 && nt_split(MODE))
       hipLaunchKernelGGL(k_splitk_finish_conv2, dim3((unsigned)(((int64_t)a.M * (a.N / 8) + 255) / 256)), dim3(256), 0,
                          stream, b);
     else if (b.S > 1)
@@ -2135,8 +2161,8 @@ extern "C" int mf_conv2d_split_pack(const float *W, int32_t Cout, int32_t Cin, i
   if (Cout <= 0 || Cin <= 0) return 0;
   if ((ks != 1 && ks != 3) || ((uintptr_t)wp & 15)) return bad("conv2d_split_pack: kernel 1 or 3, aligned output");
   const int64_t n = (int64_t)Cout * ks * ks * 3 * Cin;
-  hipLaunchKernelGGL(k_conv2_pack_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, W, Cout, Cin, ks * ks,
-                     (uint16_t *)wp);
+  hipLaunchKernelGGL(k_conv2_pack_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, W, Cout, Cin, Cin, 0,
+                     ks * ks, (uint16_t *)wp);
   return mf::check_launch("mf_conv2d_split_pack");
 }
 
@@ -2178,4 +2204,114 @@ extern "C" int mf_conv2d_split_fwd(const void *xs, const void *wp, const float *
   a.S = S; a.slab = S > 1 ? (float *)ws : nullptr;
   if (int e = launch_nt<kConv2Fwd>(a, stream)) return e;
   return mf::check_launch("mf_conv2d_split_fwd");
+}
+
+/* The volumetric part's fp32 layers as split-bf16 GEMMs (the precision contract is 8.1's): conv4 /
+ * conv3's dense channels (Convolution3D k4 s2 p1 on a channels-last grid) and the per-point 1x1 convolutions.
+ *   xs   bf16 [B][D^3][2 Cin]  (a voxel's Cin hi channels, then its Cin lo channels)
+ *   wp   bf16 [Cout][64][3 Cin] from mf_conv3d_k4s2_split_pack (input channels c_off .. c_off + Cin - 1 of W)
+ *   out  row m = (b, output voxel): v = act(conv + bias) (relu: 0 / 1), written as out32[m * ldo32 + n] and / or
+ *        outs[m * ldos + n] = hi(v), outs[m * ldos + los + n] = lo(v)
+ *   ws   mf_conv3d_k4s2_split_workspace_bytes(...) bytes of fp32 split-K slabs (0: none needed, ws may be null);
+ *        the slabs are added in slab order by the finish pass: the same bits from run to run */
+namespace {
+int split_out_check(const char *what, const float *bias, float *out32, int ldo32, void *outs, int ldos, int los, int N) {
+  if ((!out32 && !outs) || N % 8 || (out32 && (ldo32 < N || ldo32 % 8)) ||
+      (outs && (ldos < N || ldos % 8 || los < N || los % 8 || ldos < los + N)))
+    return bad(what);
+  if (((uintptr_t)bias | (uintptr_t)out32 | (uintptr_t)outs) & 15) return bad(what);
+  return 0;
+}
+}  // namespace
+
+extern "C" int mf_conv3d_k4s2_split_pack(const float *W, int32_t Cout, int32_t Cin, int32_t w_cin, int32_t c_off,
+                                         void *wp, mfStream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (Cout <= 0 || Cin <= 0) return 0;
+  if (c_off < 0 || c_off + Cin > w_cin || ((uintptr_t)wp & 15)) return bad("conv3d_k4s2_split_pack: channel range, aligned output");
+  const int64_t n = (int64_t)Cout * 64 * 3 * Cin;
+  hipLaunchKernelGGL(k_conv2_pack_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, W, Cout, Cin, w_cin,
+                     c_off, 64, (uint16_t *)wp);
+  return mf::check_launch("mf_conv3d_k4s2_split_pack");
+}
+
+extern "C" int64_t mf_conv3d_k4s2_split_workspace_bytes(int32_t B, int32_t Cin, int32_t Cout, int32_t D) {
+  Geom g;
+  if (B <= 0 || conv_geom(B, 2 * Cin, Cout, D, 4, 2, 1, 1, &g)) return 0;
+  const int64_t M = (int64_t)B * g.Do * g.Do * g.Do;
+  const int S = nt_splitk(M, Cout, 64 * 3 * Cin);
+  return S > 1 ? (int64_t)S * M * Cout * 4 : 0;
+}
+
+extern "C" int mf_conv3d_k4s2_split_fwd(const void *xs, const void *wp, const float *bias, int32_t relu, float *out32,
+                                        int32_t ldo32, void *outs, int32_t ldos, int32_t los, void *ws, int64_t ws_bytes,
+                                        int32_t B, int32_t Cin, int32_t Cout, int32_t D, mfStream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (B <= 0) return 0;
+  Geom g;
+  if (int e = conv_geom(B, 2 * Cin, Cout, D, 4, 2, 1, 1, &g)) return e;
+  if (Cin % 8 || (int64_t)Cout * 64 * 3 * Cin >= kMaxBf16Elems) return bad("conv3d_k4s2_split_fwd: Cin % 8 == 0, weights < 2^30 elements");
+  if (int e = split_out_check("conv3d_k4s2_split_fwd: an output; pitches >= Cout, multiples of 8; lo plane inside the row; 16-byte aligned",
+                              bias, out32, ldo32, outs, ldos, los, Cout))
+    return e;
+  if (((uintptr_t)xs | (uintptr_t)wp | (uintptr_t)ws) & 15) return bad("conv3d_k4s2_split_fwd: 16-byte aligned operands");
+  const int64_t M = (int64_t)B * g.Do * g.Do * g.Do;
+  int S = nt_splitk(M, Cout, 64 * 3 * Cin);
+  if (S > 1 && (!ws || ws_bytes < (int64_t)S * M * Cout * 4)) S = 1;
+  NtArgs a = {};
+  a.A = (const uint16_t *)xs; a.W = (const uint16_t *)wp; a.bias = bias;
+  a.M = (int)M; a.N = Cout; a.K = 64 * 3 * Cin; a.ldw = 64 * 3 * Cin; a.groups = 1;
+  a.B = B; a.D = D; a.Do = g.Do; a.olog = g.olog; a.Cin = 3 * Cin; a.Cout = Cout;
+  a.ks = 4; a.stride = 2; a.pad = 1; a.dil = 1;
+  a.xc = 2 * Cin; a.act = relu ? 1 : 0; a.ldo32 = ldo32; a.ldos = ldos; a.los = los;
+  a.out32 = out32; a.outs = (uint16_t *)outs;
+  a.S = S; a.slab = S > 1 ? (float *)ws : nullptr;
+  if (int e = launch_nt<kConvFwdS>(a, stream)) return e;
+  return mf::check_launch("mf_conv3d_k4s2_split_fwd");
+}
+
+/* out = act(A W^T + bias) on split operands:
+ *   As   bf16 [M][lda]: columns 0 .. Kp - 1 hi, Kp .. 2 Kp - 1 lo of the fp32 row (lda >= 2 Kp)
+ *   wp   bf16 [Np][3 Kp] from mf_linear_split_pack (Np >= N); outputs and ws as mf_conv3d_k4s2_split_fwd
+ *        (mf_linear_split_workspace_bytes(M, N, Kp)) */
+extern "C" int mf_linear_split_pack(const float *W, int64_t w_gs, int32_t ldw, int32_t N, int32_t K, int32_t Np,
+                                    int32_t Kp, int32_t groups, void *wp, mfStream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (N <= 0 || K <= 0 || groups <= 0) return 0;
+  if (Np < N || Kp < K || Kp % 8 || ldw < K || ((uintptr_t)wp & 15))
+    return bad("linear_split_pack: Np >= N, Kp >= K, Kp % 8 == 0, ldw >= K, aligned output");
+  const int64_t n = (int64_t)groups * Np * 3 * Kp;
+  hipLaunchKernelGGL(k_rows_pack_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, W, w_gs, ldw, N, K, Np,
+                     Kp, groups, (uint16_t *)wp);
+  return mf::check_launch("mf_linear_split_pack");
+}
+
+extern "C" int64_t mf_linear_split_workspace_bytes(int64_t M, int32_t N, int32_t Kp) {
+  if (M <= 0 || N <= 0 || Kp <= 0 || N % 8) return 0;
+  const int S = nt_splitk(M, N, 3 * Kp);
+  return S > 1 ? (int64_t)S * M * N * 4 : 0;
+}
+
+extern "C" int mf_linear_split_fwd(const void *As, int32_t lda, const void *wp, const float *bias, int32_t relu,
+                                   float *out32, int32_t ldo32, void *outs, int32_t ldos, int32_t los, void *ws,
+                                   int64_t ws_bytes, int32_t M, int32_t N, int32_t Kp, mfStream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (M <= 0 || N <= 0) return 0;
+  if (Kp <= 0 || Kp % 8 || lda % 8 || lda < 2 * Kp || (((uintptr_t)As | (uintptr_t)wp | (uintptr_t)ws) & 15))
+    return bad("linear_split_fwd: Kp, lda % 8 == 0, lda >= 2 Kp, 16-byte aligned operands");
+  if ((int64_t)M * lda >= kMaxBf16Elems || (int64_t)N * 3 * Kp >= kMaxBf16Elems)
+    return bad("linear_split_fwd: an operand spans >= 2^31 bytes");
+  if (int e = split_out_check("linear_split_fwd: an output; N % 8 == 0; pitches >= N, multiples of 8; lo plane inside the row; 16-byte aligned",
+                              bias, out32, ldo32, outs, ldos, los, N))
+    return e;
+  int S = nt_splitk(M, N, 3 * Kp);
+  if (S > 1 && (!ws || ws_bytes < (int64_t)S * M * N * 4)) S = 1;
+  NtArgs a = {};
+  a.A = (const uint16_t *)As; a.W = (const uint16_t *)wp; a.bias = bias;
+  a.M = M; a.N = N; a.K = 3 * Kp; a.lda = lda; a.ldw = 3 * Kp; a.groups = 1;
+  a.xc = 2 * Kp; a.act = relu ? 1 : 0; a.ldo32 = ldo32; a.ldos = ldos; a.los = los;
+  a.out32 = out32; a.outs = (uint16_t *)outs;
+  a.S = S; a.slab = S > 1 ? (float *)ws : nullptr;
+  if (int e = launch_nt<kRowsS>(a, stream)) return e;
+  return mf::check_launch("mf_linear_split_fwd");
 }

@@ -401,10 +401,13 @@ int pick_cpw(int C, int B, int64_t V) {
 // and the per-channel sum order are those of ``corners`` / k_interp_fwd_vm: identical bits.
 constexpr int kClPointsPerWave = 2;
 
+// SPLIT: the same fp32 sample, written in split-bf16 form instead (``out`` is bf16 rows of pitch ldo: hi = bf16(v) at
+// column c, lo = bf16(v - hi) at column los + c) -- the A operand of mf_linear_split_fwd.
+template <bool SPLIT>
 __global__ __launch_bounds__(kInterpThreads) void k_interp_fwd_cl(
     const float *__restrict__ vox, const float *__restrict__ points,
     const int32_t *__restrict__ batch_indices, int64_t n, int B, int C, int X, int Y, int Z,
-    float *__restrict__ out, int64_t ldo) {
+    void *__restrict__ out, int64_t ldo, int64_t los) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t V = (int64_t)X * Y * Z;
   const int64_t p0 = ((int64_t)blockIdx.x * (kInterpThreads / 64) + wave) * kClPointsPerWave;
@@ -434,7 +437,17 @@ __global__ __launch_bounds__(kInterpThreads) void k_interp_fwd_cl(
           acc.w += k.w[j] * g[j].w;
         }
       }
-      *reinterpret_cast<float4 *>(out + p * ldo + c) = acc;
+      if (SPLIT) {
+        const uint32_t h0 = mf::bf16_bits(acc.x), h1 = mf::bf16_bits(acc.y), h2 = mf::bf16_bits(acc.z),
+                       h3 = mf::bf16_bits(acc.w);
+        uint16_t *os = static_cast<uint16_t *>(out) + p * ldo + c;
+        *reinterpret_cast<uint2 *>(os) = make_uint2(h0 | h1 << 16, h2 | h3 << 16);
+        *reinterpret_cast<uint2 *>(os + los) =
+            make_uint2(mf::bf16_bits(acc.x - mf::bf16_lo(h0)) | mf::bf16_bits(acc.y - mf::bf16_lo(h1)) << 16,
+                       mf::bf16_bits(acc.z - mf::bf16_lo(h2)) | mf::bf16_bits(acc.w - mf::bf16_lo(h3)) << 16);
+      } else {
+        *reinterpret_cast<float4 *>(static_cast<float *>(out) + p * ldo + c) = acc;
+      }
     }
   }
 }
@@ -692,9 +705,29 @@ extern "C" int mf_interpolate_voxel_grid_cl_fwd(const float *vox, const float *p
     return -(int)hipErrorInvalidValue;
   }
   const int64_t per_block = (kInterpThreads / 64) * kClPointsPerWave;
-  hipLaunchKernelGGL(k_interp_fwd_cl, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(kInterpThreads), 0,
-                     stream, vox, points, batch_indices, n, B, C, X, Y, Z, out, ldo);
+  hipLaunchKernelGGL(k_interp_fwd_cl<false>, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(kInterpThreads), 0,
+                     stream, vox, points, batch_indices, n, B, C, X, Y, Z, (void *)out, ldo, (int64_t)0);
   return mf::check_launch("mf_interpolate_voxel_grid_cl_fwd");
+}
+
+/* mf_interpolate_voxel_grid_cl_fwd with the samples written in split-bf16 form: outs bf16 rows of pitch ldos, hi at
+ * column c, lo at column los + c (interpolated in fp32 exactly as the fp32 form, then split; no fp32 is written). */
+extern "C" int mf_interpolate_voxel_grid_cl_split_fwd(const float *vox, const float *points,
+                                                      const int32_t *batch_indices, int64_t n, int B, int C, int X,
+                                                      int Y, int Z, void *outs, int64_t ldos, int64_t los,
+                                                      mfStream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n <= 0) return 0;
+  if (C % 4 || ldos % 4 || los % 4 || los < C || ldos < los + C || ((uintptr_t)outs & 7) || ((uintptr_t)vox & 15)) {
+    mf::set_last_error(hipErrorInvalidValue,
+                       "interpolate_voxel_grid (channels-last, split): need C, ldos, los % 4 == 0, los >= C, ldos >= los + C, "
+                       "8-byte aligned outs");
+    return -(int)hipErrorInvalidValue;
+  }
+  const int64_t per_block = (kInterpThreads / 64) * kClPointsPerWave;
+  hipLaunchKernelGGL(k_interp_fwd_cl<true>, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(kInterpThreads), 0,
+                     stream, vox, points, batch_indices, n, B, C, X, Y, Z, outs, ldos, los);
+  return mf::check_launch("mf_interpolate_voxel_grid_cl_split_fwd");
 }
 
 /* Channels-last bf16 sampler of the training path: vox bf16 [B, X*Y*Z, C] -> out bf16 [n, ldo >= C] (C % 8 == 0,

@@ -301,10 +301,12 @@ __global__ __launch_bounds__(kRedThreads) void k_sc_reduce(ScArgs a, const float
 // channels-last trilinear sampler consume): lanes run over channels, 4 each -- a contributing
 // (row, slot) is ONE 16-byte load per lane (a whole 1 KB row segment per wave), the store is a
 // 16-byte row segment, no LDS transpose.  Same taps in the same order, then + dense + bias:
-// the same bits as k_sc_reduce.  Cout % 256 == 0, Cout <= 512.
+// the same bits as k_sc_reduce.  Cout % 256 == 0, Cout <= 512.  ``outs`` (or null): the split-bf16 form of the same
+// fp32 value, bf16 [B][Vo][2 Cout] = a voxel's hi channels (bf16(v)), then its lo channels (bf16(v - hi)) -- the
+// operand of mf_conv3d_k4s2_split_fwd, written beside the fp32 grid with no pass of its own.
 __global__ __launch_bounds__(kRedThreads) void k_sc_reduce_cl(ScArgs a, const float *__restrict__ dense,
                                                              const float *__restrict__ bias, int relu,
-                                                             float *__restrict__ out) {
+                                                             float *__restrict__ out, uint16_t *__restrict__ outs) {
   const int D = a.D, Do = D / 2, V = D * D * D, Vo = Do * Do * Do;
   const int b = blockIdx.y;
   const int o0 = blockIdx.x * 64;
@@ -367,6 +369,14 @@ __global__ __launch_bounds__(kRedThreads) void k_sc_reduce_cl(ScArgs a, const fl
         v.z = v.z > 0.0f ? v.z : 0.0f; v.w = v.w > 0.0f ? v.w : 0.0f;
       }
       *reinterpret_cast<float4 *>(out + obase + 256 * j + 4 * lane) = v;
+      if (outs) {
+        const uint32_t h0 = mf::bf16_bits(v.x), h1 = mf::bf16_bits(v.y), h2 = mf::bf16_bits(v.z), h3 = mf::bf16_bits(v.w);
+        uint16_t *os = outs + 2 * obase + 256 * j + 4 * lane;
+        *reinterpret_cast<uint2 *>(os) = make_uint2(h0 | h1 << 16, h2 | h3 << 16);
+        *reinterpret_cast<uint2 *>(os + a.Cout) =
+            make_uint2(mf::bf16_bits(v.x - mf::bf16_lo(h0)) | mf::bf16_bits(v.y - mf::bf16_lo(h1)) << 16,
+                       mf::bf16_bits(v.z - mf::bf16_lo(h2)) | mf::bf16_bits(v.w - mf::bf16_lo(h3)) << 16);
+      }
     }
   }
 }
@@ -458,14 +468,14 @@ void sc_index(const ScArgs &a, hipStream_t stream) {
 
 // 8 parity-class GEMMs + output-stationary reduce
 void sc_gemm_reduce(const ScArgs &a, const float *Wp, const float *dense, const float *bias, int relu,
-                    float *out, hipStream_t stream, int channels_last = 0) {
+                    float *out, hipStream_t stream, int channels_last = 0, uint16_t *outs = nullptr) {
   const size_t lds_g = (size_t)a.Cs * (kTM + 4 + kTN + 4) * sizeof(float);
   // persistent-style: 2 workgroups per CU walk the (class, row tile, column tile) list
   hipLaunchKernelGGL(k_sc_gemm, dim3(512), dim3(256), lds_g, stream, a, Wp);
   const int Vo = (a.D / 2) * (a.D / 2) * (a.D / 2);
   if (channels_last) {
     hipLaunchKernelGGL(k_sc_reduce_cl, dim3((Vo + 63) / 64, a.B), dim3(kRedThreads), 0, stream, a, dense, bias,
-                       relu, out);
+                       relu, out, outs);
     return;
   }
   hipLaunchKernelGGL(k_sc_reduce, dim3((Vo + 63) / 64, a.B), dim3(kRedThreads),
@@ -519,17 +529,14 @@ extern "C" int mf_sparse_conv3d_k4s2_points_fwd(const float *values, const float
   return mf::check_launch("mf_sparse_conv3d_k4s2_points_fwd");
 }
 
-extern "C" int mf_sparse_conv3d_k4s2_points_cl_fwd(const float *values, int64_t ldv, const float *points,
-                                                const int32_t *batch_indices, int64_t n, float ox,
-                                                float oy, float oz, float pitch, const float *Wp,
-                                                const float *dense, const float *bias, float *out,
-                                                void *ws, int32_t B, int32_t Cs, int32_t Cout,
-                                                int32_t D, int32_t max_rows, int32_t relu,
-                                                mfStream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+namespace {
+int sc_points_cl(const char *what, const float *values, int64_t ldv, const float *points, const int32_t *batch_indices,
+                 int64_t n, float ox, float oy, float oz, float pitch, const float *Wp, const float *dense,
+                 const float *bias, float *out, uint16_t *outs, void *ws, int32_t B, int32_t Cs, int32_t Cout, int32_t D,
+                 int32_t max_rows, int32_t relu, hipStream_t stream) {
   if (B <= 0 || max_rows <= 0) return 0;
   if (int e = sc_check(B, Cs, Cout, D)) return e;
-  if (Cout % 256 || ldv < Cs) {
+  if (Cout % 256 || ldv < Cs || ((uintptr_t)outs & 7)) {
     mf::set_last_error(hipErrorInvalidValue, "sparse_conv3d (channels-last): need Cout % 256 == 0, ldv >= Cs");
     return -(int)hipErrorInvalidValue;
   }
@@ -546,6 +553,35 @@ extern "C" int mf_sparse_conv3d_k4s2_points_cl_fwd(const float *values, int64_t 
   if (n > 0)
     hipLaunchKernelGGL(k_sc_rows_from_chains, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, w.a,
                        values, points, batch_indices, n, ox, oy, oz, pitch, w.head, w.link, ldv);
-  sc_gemm_reduce(w.a, Wp, dense, bias, relu, out, stream, 1);
-  return mf::check_launch("mf_sparse_conv3d_k4s2_points_cl_fwd");
+  sc_gemm_reduce(w.a, Wp, dense, bias, relu, out, stream, 1, outs);
+  return mf::check_launch(what);
+}
+}  // namespace
+
+extern "C" int mf_sparse_conv3d_k4s2_points_cl_fwd(const float *values, int64_t ldv, const float *points,
+                                                const int32_t *batch_indices, int64_t n, float ox,
+                                                float oy, float oz, float pitch, const float *Wp,
+                                                const float *dense, const float *bias, float *out,
+                                                void *ws, int32_t B, int32_t Cs, int32_t Cout,
+                                                int32_t D, int32_t max_rows, int32_t relu,
+                                                mfStream_t stream_) {
+  return sc_points_cl("mf_sparse_conv3d_k4s2_points_cl_fwd", values, ldv, points, batch_indices, n, ox, oy, oz, pitch,
+                      Wp, dense, bias, out, nullptr, ws, B, Cs, Cout, D, max_rows, relu, (hipStream_t)stream_);
+}
+
+/* mf_sparse_conv3d_k4s2_points_cl_fwd that also writes the split-bf16 form of its output, out_split bf16
+ * [B][(D/2)^3][2 Cout] (hi channels, then lo channels: the split of the fp32 value, bit for bit). */
+extern "C" int mf_sparse_conv3d_k4s2_points_cl_split_fwd(const float *values, int64_t ldv, const float *points,
+                                                         const int32_t *batch_indices, int64_t n, float ox, float oy,
+                                                         float oz, float pitch, const float *Wp, const float *dense,
+                                                         const float *bias, float *out, void *out_split, void *ws,
+                                                         int32_t B, int32_t Cs, int32_t Cout, int32_t D,
+                                                         int32_t max_rows, int32_t relu, mfStream_t stream_) {
+  if (!out_split) {
+    mf::set_last_error(hipErrorInvalidValue, "sparse_conv3d (channels-last, split): out_split is null");
+    return -(int)hipErrorInvalidValue;
+  }
+  return sc_points_cl("mf_sparse_conv3d_k4s2_points_cl_split_fwd", values, ldv, points, batch_indices, n, ox, oy, oz,
+                      pitch, Wp, dense, bias, out, (uint16_t *)out_split, ws, B, Cs, Cout, D, max_rows, relu,
+                      (hipStream_t)stream_);
 }
