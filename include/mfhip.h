@@ -912,6 +912,33 @@ int mf_full_grids(const double *points, const int64_t *p_off, const double *T, c
                   const double *origin, int32_t n_examples, int64_t total_points, int32_t dim,
                   int32_t *target_full, int32_t *nontarget_full, mfStream_t stream);
 
+/* ---- training-time augmentation (datasets/augmentation.py, csrc/augment.hip) -----------------------
+ * RGBDPoseEstimationDatasetReIndexedBase._augment_rgbd for n examples of S x S pixels (S a multiple of 8 in
+ * 8..256) per call.  rgb uint8 [n, S, S, 3]; pcd float32 or float64 [n, S, S, 3] (pcd_is_f64), NaN invalid;
+ * params float64 [n, 12], drawn on the host: cut case, cut uniform, blob-count uniform, contrast alpha, H, S, V
+ * multipliers, blur sigma, resize scale, example key, 2 reserved.  Per-pixel / per-component words come from
+ * Philox4x32-10 keyed by (seed & 0xffffffff, example key), counter (pixel, stream, 0, 0).  Outputs and workspace
+ * are the caller's; nothing is allocated or synchronised.  DESIGN.md "Augmentation". */
+/* Host-only: bytes of the workspace (16-byte aligned) of mf_augment_mask / mf_augment_rgb; < 0: bad size. */
+int64_t mf_augment_workspace_bytes(int32_t n, int32_t S);
+/* _augment_mask: valid mask -> one-sided cut -> 8-connected components (one workgroup per example, labels in
+ * LDS) -> largest + the K = floor(u m) components with the smallest words -> crop to the kept mask's box and
+ * imgviz.centerize back to S x S.  kept_mask uint8 [n, S, S] (before re-centring); stats int32 [n, 12]: final
+ * box y1 x1 y2 x2, components m, drawn K, largest component's id, kept pixels, cut box y1 x1 y2 x2;
+ * keep uint8 [n]: 0 = the mask was empty at some step and the outputs are pure padding.  labels / sizes
+ * (int32 [n, S, S], may be NULL): every pixel's component id (its first pixel in raster order, -1 outside the cut
+ * mask) and that component's pixel count. */
+int mf_augment_mask(const uint8_t *rgb, const void *pcd, int32_t pcd_is_f64, const double *params,
+                    int32_t n, int32_t S, int64_t seed, uint8_t *rgb_out, void *pcd_out,
+                    uint8_t *kept_mask, int32_t *stats, uint8_t *keep, int32_t *labels, int32_t *sizes,
+                    void *workspace, mfStream_t stream);
+/* _augment_rgb: linear contrast, HSV multipliers, 5 x 5 Gaussian blur, bicubic resize down and back. */
+int mf_augment_rgb(const uint8_t *rgb, const double *params, int32_t n, int32_t S, uint8_t *rgb_out,
+                   void *workspace, mfStream_t stream);
+/* _augment_pcd: 5 % pixel drop-out, then + 0.003 z per coordinate (z standard normal, float64). */
+int mf_augment_pcd(const void *pcd, int32_t pcd_is_f64, const double *params, int32_t n, int32_t S,
+                   int64_t seed, void *pcd_out, mfStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

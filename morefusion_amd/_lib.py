@@ -206,6 +206,10 @@ _SIGNATURES = {
     "mf_render_raster": ([_p, _i64, _p], _i),
     "mf_render_resolve": ([_p, _i64, _p], _i),
     "mf_full_grids": ([_p] * 5 + [_i, _i64, _i, _p, _p, _p], _i),
+    "mf_augment_workspace_bytes": ([_i, _i], _i64),
+    "mf_augment_mask": ([_p, _p, _i, _p, _i, _i, _i64] + [_p] * 9, _i),
+    "mf_augment_rgb": ([_p, _p, _i, _i, _p, _p, _p], _i),
+    "mf_augment_pcd": ([_p, _i, _p, _i, _i, _i64, _p, _p], _i),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

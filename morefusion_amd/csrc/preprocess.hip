@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "mf_common.h"
+#include "mf_centerize.h"
 
 namespace {
 
@@ -81,24 +82,6 @@ __global__ __launch_bounds__(kStatsThreads) void k_pre_stats(
   }
 }
 
-// cv::resize INTER_LINEAR source index + fixed-point weights for one destination index
-// (modules/imgproc/src/resize.cpp, resizeGeneric_ set-up): f = (float)((d+0.5)*scale-0.5),
-// s = floor(f), f -= s; clamped at both borders; weights = short(rint(w * 2048)).
-__device__ __forceinline__ void linear_tap(int d, double scale, int ssize, int &s0, int &s1,
-                                           int &w0, int &w1, const bool zero_frac_at_border) {
-  float f = (float)(((double)d + 0.5) * scale - 0.5);
-  int s = (int)floorf(f);
-  f -= (float)s;
-  if (zero_frac_at_border) {  // the x direction resets the fraction, y only clamps the rows
-    if (s < 0) { f = 0.0f; s = 0; }
-    if (s >= ssize - 1) { f = 0.0f; s = ssize - 1; }
-  }
-  w0 = (int)(short)rintf((1.0f - f) * 2048.0f);
-  w1 = (int)(short)rintf(f * 2048.0f);
-  s0 = min(max(s, 0), ssize - 1);
-  s1 = min(max(s + 1, 0), ssize - 1);
-}
-
 __global__ __launch_bounds__(256) void k_pre_crops(
     const uint8_t *__restrict__ rgb, const float *__restrict__ depth,
     const int32_t *__restrict__ label, int H, int W, double fx, double fy, double cx, double cy,
@@ -119,29 +102,15 @@ __global__ __launch_bounds__(256) void k_pre_crops(
   ro[0] = 0; ro[1] = 0; ro[2] = 0;
   po[0] = nanv; po[1] = nanv; po[2] = nanv;
   if (!ok) return;
-  // imgviz.centerize: scale = min(S/sh, S/sw); resized size = round(size*scale) (half-even)
-  int dh = S, dw = S, ph = 0, pw = 0;
-  const bool identity = (sh == S && sw == S);
-  if (!identity) {
-    const double scale_h = 1.0 * S / sh, scale_w = 1.0 * S / sw;
-    const double scale = scale_h < scale_w ? scale_h : scale_w;
-    dh = (int)rint(sh * scale);
-    dw = (int)rint(sw * scale);
-    if (dh < S) ph = (S - dh) / 2;
-    if (dw < S) pw = (S - dw) / 2;
-  }
-  const int dy = oy - ph, dx = ox - pw;
-  if (dy < 0 || dy >= dh || dx < 0 || dx >= dw || dh <= 0 || dw <= 0) return;  // padding
+  const mf::Centerize g = mf::centerize_geometry(sh, sw, S);  // imgviz.centerize (include/mf_centerize.h)
+  int dy, dx;
+  if (!mf::centerize_inside(g, oy, ox, dy, dx)) return;  // padding
   auto masked = [&](int yy, int xx) { return label[(int64_t)(y1 + yy) * W + (x1 + xx)] == id; };
 
-  // ---- points: cv::resize INTER_NEAREST: s = min(floor(d * (1/(dsize/ssize))), ssize-1)
+  // ---- points: cv::resize INTER_NEAREST
   {
-    int sy = dy, sx = dx;
-    if (!identity) {
-      const double ify = 1.0 / ((double)dh / sh), ifx = 1.0 / ((double)dw / sw);
-      sy = min((int)floor(dy * ify), sh - 1);
-      sx = min((int)floor(dx * ifx), sw - 1);
-    }
+    int sy, sx;
+    mf::centerize_nearest(g, dy, dx, sh, sw, sy, sx);
     if (masked(sy, sx)) {
       const int r = y1 + sy, c = x1 + sx;
       const float z = depth[(int64_t)r * W + c];
@@ -156,31 +125,7 @@ __global__ __launch_bounds__(256) void k_pre_crops(
   auto pix = [&](int yy, int xx, int c) -> int {
     return masked(yy, xx) ? (int)rgb[((int64_t)(y1 + yy) * W + (x1 + xx)) * 3 + c] : 0;
   };
-  if (identity) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) ro[c] = (uint8_t)pix(dy, dx, c);
-    return;
-  }
-  const double scale_x = 1.0 / ((double)dw / sw), scale_y = 1.0 / ((double)dh / sh);
-  const bool area2 = fabs(scale_x - 2.0) < 2.220446049250313e-16 &&
-                     fabs(scale_y - 2.0) < 2.220446049250313e-16;
-  if (area2) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      ro[c] = (uint8_t)((pix(2 * dy, 2 * dx, c) + pix(2 * dy, 2 * dx + 1, c) +
-                         pix(2 * dy + 1, 2 * dx, c) + pix(2 * dy + 1, 2 * dx + 1, c) + 2) >> 2);
-    return;
-  }
-  int xa, xb, a0, a1, ya, yb, b0, b1;
-  linear_tap(dx, scale_x, sw, xa, xb, a0, a1, true);
-  linear_tap(dy, scale_y, sh, ya, yb, b0, b1, false);
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int r0 = pix(ya, xa, c) * a0 + pix(ya, xb, c) * a1;  // horizontal pass, row ya
-    const int r1 = pix(yb, xa, c) * a0 + pix(yb, xb, c) * a1;  // row yb
-    const int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
-    ro[c] = (uint8_t)min(max(v, 0), 255);
-  }
+  mf::centerize_linear_u8(g, dy, dx, sh, sw, pix, ro);
 }
 
 

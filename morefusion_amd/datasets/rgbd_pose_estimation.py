@@ -45,8 +45,11 @@ class RGBDPoseEstimationDatasetBase:
         if class_ids is not None:
             class_ids = tuple(class_ids)
         self._class_ids = class_ids
+        self._ids = []  # one image id per frame (datasets.reindex names the example files after them)
 
     def __len__(self):
+        if self._ids:
+            return len(self._ids)
         raise NotImplementedError
 
     def get_frame(self, index):
