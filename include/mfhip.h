@@ -749,6 +749,65 @@ int mf_occmap_extract(const mfOccTree *trees, int32_t n_trees, const int32_t *ta
                       int32_t D2, float *grid_target, float *grid_nontarget, float *grid_empty,
                       uint8_t *net_target, uint8_t *net_nte, mfStream_t stream);
 
+/* ---- instance tracking across frames (contrib/instance_tracking.py, csrc/occtrack.hip) -------
+ * The per-frame loop of the reference's map server: render the instance maps (mfOccTree boxes)
+ * into the current camera, match the detector's ids against the rendering, clean both label
+ * images and merge them (DESIGN.md "Instance tracking").  Label images are [H, W] int32: >= 0 an
+ * instance id, -1 background, -2 uncertain.  `ref_ids` / `det_ids`: the ids the host knows may
+ * occur in the rendered / detected image, each ASCENDING and without repeats (<= 1024).
+ * Every call is asynchronous, allocates nothing and never synchronises; all results are bitwise
+ * independent of the order in which lanes run. */
+/* Host-only: bytes of `workspace` (16-byte aligned) shared by render, clean and merge; < 0: bad size. */
+int64_t mf_occtrack_workspace_bytes(int32_t H, int32_t W, int32_t n_ref);
+/* Host-only: int32 elements of `stats` for mf_occtrack_overlap / mf_occtrack_assign: inter
+ * [n_ref, n_det], per reference id {area, edge, non-edge}, per detection {area, edge, non-edge},
+ * per detection {min row, min col, max row, max col} ({INT_MAX x2, INT_MIN x2} when absent). */
+int64_t mf_occtrack_stats_elems(int32_t n_ref, int32_t n_det);
+/* out [n, 3] := T [4, 4] (row-major float32, DEVICE) applied to pts [n, 3] in float32:
+ * ((T0 x + T1 y) + T2 z) + T3 per row, no contraction; NaN rows stay NaN. */
+int mf_occtrack_transform(const float *pts, const float *T, int64_t n, float *out, mfStream_t stream);
+/* castRay of every stride-2 pixel into every listed tree: pts [H * W, 3] in the map frame (NaN
+ * rows: the ray through the pixel at z = 1, from K [3, 3] and sensor->map T [4, 4], both DEVICE
+ * float32); slots [n_slots, 2] int32 = {tree index, instance id}.  The nearest hit wins, an exact
+ * tie goes to the earlier slot.  label_rendered [H, W] (-2: no hit; the winner of pixel (j, i)
+ * covers rows j-1..j, columns i-1..i); depth_rendered [H, W] float32: the winner's distance at
+ * the stride-2 pixels, NaN elsewhere. */
+int mf_occtrack_render(const float *pts, const float *K, const float *T, float origin_x, float origin_y,
+                       float origin_z, const mfOccTree *trees, const int32_t *slots, int32_t n_slots,
+                       int32_t H, int32_t W, void *workspace, int32_t *label_rendered,
+                       float *depth_rendered, mfStream_t stream);
+/* One pass over both images -> stats (layout above).  The edge band is the complement of the
+ * rectangle (int(0.1 W), int(0.1 H)) .. (int(0.9 W), int(0.9 H)), corners included. */
+int mf_occtrack_overlap(const int32_t *label_rendered, const int32_t *label_detected, int32_t H, int32_t W,
+                        const int32_t *ref_ids, int32_t n_ref, const int32_t *det_ids, int32_t n_det,
+                        int32_t *stats, mfStream_t stream);
+/* remap [n_det + 1] := the tracked id of every detection (-2: suspicious; a new id from *counter
+ * where IoU < iou_threshold and coverage < coverage_threshold), remap[n_det] := the updated
+ * counter, also stored to *counter (the float32 quotients are compared in double, as the
+ * reference compares them with its double literals).  suspicious_ref [n_ref] := edge > non-edge; suspicious_det
+ * [n_det] := 1 (edge rule) | 2 (size rule: area < min_mask^2, box area < min_bbox^2 or a box
+ * side < min_side). */
+int mf_occtrack_assign(const int32_t *stats, const int32_t *ref_ids, int32_t n_ref, int32_t n_det, int32_t H,
+                       int32_t W, int32_t min_mask, int32_t min_bbox, int32_t min_side, double iou_threshold,
+                       double coverage_threshold, int32_t *counter, int32_t *remap, int32_t *suspicious_ref,
+                       int32_t *suspicious_det, mfStream_t stream);
+/* label_tracked := remap applied to label_detected (negative pixels in the edge band and
+ * suspicious ids -> -2); label_reference := label_rendered with suspicious reference ids -> -2. */
+int mf_occtrack_relabel(const int32_t *label_rendered, const int32_t *label_detected, int32_t H, int32_t W,
+                        const int32_t *ref_ids, int32_t n_ref, const int32_t *det_ids, int32_t n_det,
+                        const int32_t *remap, const int32_t *suspicious_ref, int32_t *label_tracked,
+                        int32_t *label_reference, mfStream_t stream);
+/* label_out := label with every 8-connected component (of equal values >= 0) below min_area
+ * pixels set to -2, then every pixel whose (2 band + 1)^2 window holds two different values or
+ * leaves the image set to -2.  label_out must not alias label. */
+int mf_occtrack_clean(const int32_t *label, int32_t H, int32_t W, int32_t min_area, int32_t band,
+                      void *workspace, int32_t *label_out, mfStream_t stream);
+/* label_merged := -2, then for each id >= 0 of label_reference in ascending order the mask of
+ * that id in label_tracked if it occurs there, else its mask in label_reference. */
+int mf_occtrack_merge(const int32_t *label_reference, const int32_t *label_tracked, int32_t H, int32_t W,
+                      const int32_t *ref_ids, int32_t n_ref, void *workspace, int32_t *label_merged,
+                      mfStream_t stream);
+
 /* ---- point-to-point ICP registration (contrib/icp_registration.py, csrc/icpreg.hip) ---------
  * open3d's voxel_down_sample + registration_icp(PointToPoint, no scaling), restated in float64
  * (DESIGN.md "ICP registration").  Point sets are packed double [n, 3] rows with int64 [n_sets + 1]

@@ -194,6 +194,15 @@ _SIGNATURES = {
     "mf_occmap_count_hits": ([_p, _i64, _p, _i, _p, _p], _i),
     "mf_occmap_apply": ([_p, _i, _i64, _i, _p], _i),
     "mf_occmap_extract": ([_p, _i, _p, _p, _p] + [_i] * 4 + [_p] * 6, _i),
+    "mf_occtrack_workspace_bytes": ([_i] * 3, _i64),
+    "mf_occtrack_stats_elems": ([_i, _i], _i64),
+    "mf_occtrack_transform": ([_p, _p, _i64, _p, _p], _i),
+    "mf_occtrack_render": ([_p, _p, _p, _f, _f, _f, _p, _p, _i, _i, _i, _p, _p, _p, _p], _i),
+    "mf_occtrack_overlap": ([_p, _p, _i, _i, _p, _i, _p, _i, _p, _p], _i),
+    "mf_occtrack_assign": ([_p, _p] + [_i] * 7 + [_d, _d] + [_p] * 5, _i),
+    "mf_occtrack_relabel": ([_p, _p, _i, _i, _p, _i, _p, _i] + [_p] * 5, _i),
+    "mf_occtrack_clean": ([_p] + [_i] * 4 + [_p, _p, _p], _i),
+    "mf_occtrack_merge": ([_p, _p, _i, _i, _p, _i, _p, _p, _p], _i),
     "mf_icpreg_workspace_bytes": ([_i64, _i64, _i64], _i64),
     "mf_icpreg_bounds": ([_p, _p, _i, _d, _p, _p, _p], _i),
     "mf_icpreg_prepare": ([_p, _p, _i, _d, _p, _p, _p, _i64, _p, _p, _i64, _d, _i64] + [_p] * 7, _i),

@@ -7,3 +7,5 @@ from .occupancy_registration import OccupancyRegistration, OccupancyRegistration
 from . import singleview_3d
 from .multi_instance_octree_mapping import MultiInstanceOctreeMapping
 from .icp_registration import ICPRegistration, icp_registration_batch
+from .instance_tracking import InstanceTracker, render_instance_maps, track_instance_ids
+from .object_mapping import ObjectMapping

@@ -24,6 +24,7 @@ from .. import _lib
 
 _KEY_MAX = 32768  # octomap's tree_max_val
 _MAX_SCANS = 32   # scan bits per cell and launch
+BACKGROUND_ID = 0  # the background map of integrate_frame / integrate_tracked_frame (pitch 0.01)
 
 
 def _key(c, res_factor):
@@ -158,6 +159,29 @@ class MultiInstanceOctreeMapping:
             slots = (fg if k == 0 else []) + [(u, bg_tree, s) for s, u in enumerate(chunk)]
             self._raycast(pts, label, slots, origin)
             self._apply(mode=0)
+
+    def integrate_tracked_frame(self, pcd, label_tracked, instance_id_to_class_id, pitch_of, origin=(0, 0, 0)):
+        """``insertScan`` for frame k >= 0 of a tracked sequence (contrib.InstanceTracker): ``pcd`` [H,W,3] in the MAP
+        frame seen from ``origin``, ``label_tracked`` [H,W] with tracked instance ids >= 1, -1 = background (one scan
+        of the background map ``BACKGROUND_ID``, pitch 0.01) and -2 = uncertain (skipped).  Every id of
+        ``instance_id_to_class_id`` that has no map yet gets one of pitch ``pitch_of(class_id)``, in ascending id,
+        then the background map; each map takes one scan of its pixels: one bounds + one ray-cast + one apply
+        launch, and no read-back beyond the bounds."""
+        get_pitch = pitch_of.__getitem__ if isinstance(pitch_of, dict) else pitch_of
+        ids = sorted(int(i) for i in instance_id_to_class_id)
+        if ids and ids[0] <= BACKGROUND_ID:
+            raise ValueError("tracked instance ids must be >= 1")
+        for i in ids:
+            if i not in self._trees:
+                self.initialize(i, pitch=get_pitch(int(instance_id_to_class_id[i])))
+        if BACKGROUND_ID not in self._trees:
+            self.initialize(BACKGROUND_ID, pitch=0.01)
+        pts = self._points(pcd)
+        label = self._device(label_tracked).reshape(-1).to(torch.int32).contiguous()
+        if label.numel() != pts.shape[0]:
+            raise ValueError("label_tracked and pcd differ in size")
+        slots = [(i, self._index(i), 0) for i in ids] + [(-1, self._index(BACKGROUND_ID), 0)]
+        self._scans(pts, label, slots, origin)
 
     def get_target_grids_batch(self, target_ids, pitch, origin, dimensions=(32, 32, 32), network_inputs=False):
         """B grids at once: target_ids [B], pitch [B], origin [B,3] (float64 arithmetic for the voxel centres).

@@ -32,10 +32,10 @@
 #include <algorithm>
 
 #include "mf_common.h"
+#include "occmap_keys.h"
 
 namespace {
 
-constexpr int kKeyMax = 32768;  // octomap's tree_max_val (16-bit keys, depth 16)
 constexpr int kThreads = 256;
 constexpr int kMaxBoundTrees = 256;  // LDS bounds table of k_occ_bounds
 constexpr int kBoundBlocks = 256;
@@ -52,20 +52,6 @@ __device__ __forceinline__ float clamp_add(float l, float u) {  // OccupancyOcTr
   if (l < kLoMin) return kLoMin;
   if (l > kLoMax) return kLoMax;
   return l;
-}
-
-// OcTreeBaseImpl::coordToKeyChecked: false outside the 16-bit key range
-__device__ __forceinline__ bool coord_key(float c, double rf, int &key) {
-  const double s = floor((double)c * rf);
-  if (!(s >= -(double)kKeyMax && s < (double)kKeyMax)) return false;  // also NaN
-  key = (int)s + kKeyMax;
-  return true;
-}
-
-__device__ __forceinline__ int64_t cell_of(const mfOccTree &t, int kx, int ky, int kz) {
-  const int x = kx - t.lo[0], y = ky - t.lo[1], z = kz - t.lo[2];
-  if (x < 0 || y < 0 || z < 0 || x >= t.dim[0] || y >= t.dim[1] || z >= t.dim[2]) return -1;
-  return ((int64_t)x * t.dim[1] + y) * t.dim[2] + z;
 }
 
 __device__ __forceinline__ int find_slot(const int32_t *slots, int n_slots, int32_t label) {

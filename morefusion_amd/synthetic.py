@@ -355,6 +355,78 @@ def make_occupancy_frame(seed=0, height=480, width=640, n_objects=8):
     return dict(rgb=rgb, depth=depth, K=K, label=label, instance_ids=instance_ids, class_ids=class_ids)
 
 
+def make_tracking_sequence(seed=0, n_frames=3, height=480, width=640, n_objects=8, appear_at=None, max_shift=0.04,
+                           max_angle=0.04):
+    """One scene of ``make_occupancy_frame``'s kind (spheres and boxes on a table in front of a wall, in the MAP
+    frame) seen from ``n_frames`` moving cameras, for the instance-tracking row: frame 0's camera sits at the map's
+    origin, the later ones are shifted by up to ``max_shift`` m and turned by up to ``max_angle`` rad.  The detector's
+    ids are a fresh random permutation per frame (ids 0 .. n-1 of the objects in view; -1 = background).
+    ``appear_at`` {object index: first frame} keeps an object out of the earlier frames.  Returns a list of
+    dict(rgb u8 [H,W,3], depth f32 [H,W] (NaN holes), label_detected i32 [H,W], K [3,3] float64, T_sensor_to_map
+    [4,4] float64, class_ids_by_detection {detection id: class id}, object_of_detection {detection id: object index},
+    class_ids i32 [n_objects])."""
+    rs = np.random.RandomState(seed)
+    appear_at = dict(appear_at or {})
+    s = width / 640.0
+    K = np.array([[619.4 * s, 0, width / 2 - 0.3], [0, 618.9 * s, height / 2 + 0.7], [0, 0, 1]])
+    v, u = np.mgrid[:height, :width].astype(np.float64)
+    d_cam = np.stack([(u - K[0, 2]) / K[0, 0], (v - K[1, 2]) / K[1, 1], np.ones_like(u)], -1)  # unit z: t = depth
+    table_y, wall_z = 0.2, 1.4
+    class_ids = rs.choice(sorted(CLASS_PITCH), n_objects, replace=False).astype(np.int32)
+    shapes = []
+    for i in range(n_objects):
+        x = -0.35 + 0.7 * (i + rs.uniform(0.2, 0.8)) / n_objects
+        z = rs.uniform(0.7, 1.15)
+        r = rs.uniform(0.03, 0.06)
+        if i % 2 == 0:
+            shapes.append(("sphere", np.array([x, table_y - r, z]), r))
+        else:
+            shapes.append(("box", np.array([x - r, table_y - rs.uniform(1.0, 2.5) * r, z - r]),
+                           np.array([x + r, table_y, z + r])))
+    palette = rs.randint(0, 256, (n_objects + 2, 3)).astype(np.uint8)
+    frames = []
+    for k in range(n_frames):
+        T = np.eye(4)
+        if k > 0:
+            T[:3, :3] = random_rotation(rs, max_angle)
+            T[:3, 3] = rs.uniform(-max_shift, max_shift, 3)
+        o, d = T[:3, 3], d_cam @ T[:3, :3].T
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t_best = np.where(d[..., 2] > 0, (wall_z - o[2]) / d[..., 2], np.inf)
+            t_table = np.where(d[..., 1] > 0, (table_y - o[1]) / d[..., 1], np.inf)
+        obj = np.full((height, width), -1, np.int32)
+        t_best = np.minimum(t_best, t_table)
+        dd = (d * d).sum(-1)
+        for i, shape in enumerate(shapes):
+            if appear_at.get(i, 0) > k:
+                continue
+            if shape[0] == "sphere":
+                c = shape[1] - o
+                b = (d * c).sum(-1)
+                disc = b * b - dd * (c @ c - shape[2] ** 2)
+                with np.errstate(invalid="ignore"):
+                    t = np.where(disc >= 0, (b - np.sqrt(disc)) / dd, np.inf)
+            else:
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    t1, t2 = (shape[1] - o) / d, (shape[2] - o) / d
+                tn = np.nanmax(np.minimum(t1, t2), -1)
+                tf = np.nanmin(np.maximum(t1, t2), -1)
+                t = np.where((tn <= tf) & (tf > 0), tn, np.inf)
+            hit = (t > 0) & (t < t_best)
+            t_best[hit], obj[hit] = t[hit], i
+        depth = np.where(np.isfinite(t_best), t_best, np.nan).astype(np.float32)
+        depth[rs.uniform(size=depth.shape) < 0.03] = np.nan
+        seen = [int(i) for i in np.unique(obj) if i >= 0]
+        det_of = dict(zip(seen, rs.permutation(len(seen)).tolist()))
+        lut = np.full(n_objects + 1, -1, np.int32)
+        for i, det in det_of.items():
+            lut[i] = det
+        frames.append(dict(rgb=palette[obj + 1], depth=depth, label_detected=lut[obj], K=K, T_sensor_to_map=T,
+                           class_ids_by_detection={det: int(class_ids[i]) for i, det in det_of.items()},
+                           object_of_detection={det: i for i, det in det_of.items()}, class_ids=class_ids))
+    return frames
+
+
 def quad_mesh(p00, p10, p11, p01):
     """Two triangles over the corners p00 -> p10 -> p11 -> p01."""
     return np.asarray([p00, p10, p11, p01], np.float64), np.asarray([[0, 1, 2], [0, 2, 3]], np.int32)
