@@ -592,6 +592,11 @@ int mf_rgb_normalize(const void *rgb, int32_t u8, const float *mean3, const floa
 int mf_bn_act_fwd(const void *x, const void *identity, const float *mean, const float *var, const float *weight,
                   const float *bias, float eps, void *y, int64_t n, int32_t C, int64_t HW, int32_t channels_last,
                   int32_t relu, int32_t bf16, mfStream_t stream);
+/* Which kernel the most recent mf_upsample_bilinear_cl_bwd / mf_bn_act_fwd launch of this process took (a host-side
+ * integer, 0 before the first launch; a refused call leaves it alone):
+ *   resize backward  1 direct gather (k_up_bwd)   2 LDS tile (k_up_bwd_tile_bf16)   3 small input map (k_up_bwd_small)
+ *   BatchNorm        16 generic (k_bn_act, either layout)   32 + ppt per channel group (k_bn_act_cl, ppt = 1 / 2 / 4) */
+int mf_backbone2d_last_path(void);
 int64_t mf_prelu_bwd_workspace_floats(int64_t n);
 int mf_prelu_bwd(const void *x, const void *dy, const float *slope, void *dx, float *dslope, float *ws, int64_t n,
                  int32_t bf16, mfStream_t stream);

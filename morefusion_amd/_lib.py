@@ -171,6 +171,7 @@ _SIGNATURES = {
     "mf_prelu_fwd": ([_p, _p, _p, _i64, _i, _p], _i),
     "mf_rgb_normalize": ([_p, _i, _p, _p, _p, _i64, _p], _i),
     "mf_bn_act_fwd": ([_p, _p, _p, _p, _p, _p, _f, _p, _i64, _i, _i64, _i, _i, _i, _p], _i),
+    "mf_backbone2d_last_path": ([], _i),
     "mf_prelu_bwd_workspace_floats": ([_i64], _i64),
     "mf_prelu_bwd": ([_p, _p, _p, _p, _p, _p, _i64, _i, _p], _i),
     "mf_gemm_bf16_last_tile": ([], _i),

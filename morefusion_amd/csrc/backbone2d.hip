@@ -488,6 +488,10 @@ __global__ __launch_bounds__(256) void k_prelu_finish(const float *__restrict__ 
   if (threadIdx.x == 0) da[0] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
 }
 
+// which kernel the last mf_upsample_bilinear_cl_bwd / mf_bn_act_fwd launch of this process took: mf_backbone2d_last_path
+enum { kPathUpDirect = 1, kPathUpTile = 2, kPathUpSmall = 3, kPathBnGeneric = 16, kPathBnGroup = 32 /* + ppt */ };
+int g_b2d_last_path = 0;
+
 int bad2d(const char *msg) {
   mf::set_last_error(hipErrorInvalidValue, msg);
   return -(int)hipErrorInvalidValue;
@@ -548,6 +552,7 @@ extern "C" int mf_upsample_bilinear_cl_bwd(const void *gy, void *gx, int32_t B, 
   const unsigned nb = (unsigned)((total + 255) / 256);
   if (C % 64 == 0 && (int64_t)H * W <= 64 && (int64_t)Ho * Wo >= 16 * (int64_t)H * W) {  // small input, large footprints
     const dim3 grid((unsigned)(H * W), (unsigned)(C / 64), (unsigned)B);
+    g_b2d_last_path = kPathUpSmall;
     if (bf16) hipLaunchKernelGGL(k_up_bwd_small<true>, grid, dim3(512), 0, stream, gy, gx, H, W, Ho, Wo, C);
     else hipLaunchKernelGGL(k_up_bwd_small<false>, grid, dim3(512), 0, stream, gy, gx, H, W, Ho, Wo, C);
     return mf::check_launch("mf_upsample_bilinear_cl_bwd");
@@ -559,11 +564,13 @@ extern "C" int mf_upsample_bilinear_cl_bwd(const void *gy, void *gx, int32_t B, 
     const size_t lds = (size_t)rows * cols * 128;
     if (lds <= 64 * 1024) {
       const int tx = (W + kUpT - 1) / kUpT, ty = (H + kUpT - 1) / kUpT;
+      g_b2d_last_path = kPathUpTile;
       hipLaunchKernelGGL(k_up_bwd_tile_bf16, dim3((unsigned)(tx * ty), (unsigned)(C / 64), (unsigned)B), dim3(512), lds, stream,
                          (const uint16_t *)gy, (uint16_t *)gx, H, W, Ho, Wo, C, tx);
       return mf::check_launch("mf_upsample_bilinear_cl_bwd");
     }
   }
+  g_b2d_last_path = kPathUpDirect;
   if (bf16) hipLaunchKernelGGL(k_up_bwd<true>, dim3(nb), dim3(256), 0, stream, gy, gx, B, H, W, Ho, Wo, C / 8);
   else hipLaunchKernelGGL(k_up_bwd<false>, dim3(nb), dim3(256), 0, stream, gy, gx, B, H, W, Ho, Wo, C / 8);
   return mf::check_launch("mf_upsample_bilinear_cl_bwd");
@@ -636,6 +643,7 @@ extern "C" int mf_bn_act_fwd(const void *x, const void *identity, const float *m
     int ppt = 1;  // pixels per lane: as many as still leave >= 2048 workgroups (8 per CU), at most 4
     while (ppt < 4 && npix / (ppb * ppt * 2) >= 2048) ppt *= 2;
     const unsigned nbp = (unsigned)((npix + ppb * ppt - 1) / (ppb * ppt));
+    g_b2d_last_path = kPathBnGroup + ppt;
     if (bf16) hipLaunchKernelGGL(k_bn_act_cl<true>, dim3(nbp), dim3(256), 0, stream, x, identity, mean, var, weight, bias,
                                  eps, y, npix, G, ppt, relu);
     else hipLaunchKernelGGL(k_bn_act_cl<false>, dim3(nbp), dim3(256), 0, stream, x, identity, mean, var, weight, bias, eps,
@@ -643,6 +651,7 @@ extern "C" int mf_bn_act_fwd(const void *x, const void *identity, const float *m
     return mf::check_launch("mf_bn_act_fwd");
   }
   const unsigned nb = (unsigned)((n / 8 + 255) / 256);
+  g_b2d_last_path = kPathBnGeneric;
 #define MF_BN_LAUNCH(BF, CL_)                                                                                   \
   hipLaunchKernelGGL((k_bn_act<BF, CL_>), dim3(nb), dim3(256), 0, stream, x, identity, mean, var, weight, bias, eps, y, \
                      n / 8, C, HW, relu)
@@ -651,6 +660,8 @@ extern "C" int mf_bn_act_fwd(const void *x, const void *identity, const float *m
 #undef MF_BN_LAUNCH
   return mf::check_launch("mf_bn_act_fwd");
 }
+
+extern "C" int mf_backbone2d_last_path(void) { return g_b2d_last_path; }
 
 /* (rgb / 255 - mean) / std of a [B, H, W, 3] image, uint8 (u8 = 1) or float32, -> float32 [B, H, W, 3]. */
 extern "C" int mf_rgb_normalize(const void *rgb, int32_t u8, const float *mean3, const float *std3, float *out,

@@ -106,3 +106,68 @@ def test_rgb_normalisation_in_one_launch_is_bit_equal_to_the_composite(ops, dtyp
     ref = (x / 255.0 - torch.tensor(R.mean_rgb).view(1, 3, 1, 1)) / torch.tensor(R.std_rgb).view(1, 3, 1, 1)
     assert y.shape == ref.shape and y.stride() == ref.stride()
     assert torch.equal(y, ref)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Per element against float64 references (tests/decoder2d_ref.py, tests/decoder2d_cases.py; the same cases run on the
+# MI355X in tests/test_gpu_backbone2d.py), every case asserting its branch through mf_backbone2d_last_path().
+# NOT run on the emulator: the two BatchNorm cases at C = 2048 with 4096 and 8193 pixels (ppt = 2 and 4 of
+# k_bn_act_cl) -- 8 and 17 million elements through one fiber per lane; they run on the GPU only.
+import decoder2d_cases as D  # noqa: E402
+import decoder2d_ref as R  # noqa: E402
+
+
+@pytest.fixture()
+def L2d():
+    return emul.build(["backbone2d.hip"])
+
+
+def _st():
+    return None
+
+
+def test_resize_mirror_vs_torch_float64():
+    """The float32 mirror of the index / weight arithmetic (decoder2d_ref.axis_taps) against torch's own bilinear
+    resize in float64: they differ only by the float32 rounding of the source coordinate -- the allowance is derived
+    in decoder2d_ref's docstring (|d weight| <= 2^-23 max(H, W) + 2^-24 per axis)."""
+    gen = torch.Generator().manual_seed(0)
+    for (B, C, H, W), (Ho, Wo) in D.RESIZE_MIRROR_SHAPES:
+        x = torch.randn(B, C, H, W, generator=gen).double().requires_grad_(True)
+        y = F.interpolate(x, (Ho, Wo), mode="bilinear", align_corners=True)
+        g = torch.randn(y.shape, generator=gen).double()
+        y.backward(g)
+        fwd, _ = R.resize_fwd_ref(x, Ho, Wo)
+        bwd, _ = R.resize_bwd_ref(g, H, W)
+        tol_f, tol_b = R.mirror_allowance(H, W, Ho, Wo, float(x.detach().abs().max()), float(g.abs().max()))
+        ef, eb = float((fwd - y.detach()).abs().max()), float((bwd - x.grad).abs().max())
+        print(f"DECODER2D mirror {(B, C, H, W)}->{(Ho, Wo)}: fwd {ef:.3e} <= {tol_f:.3e}, bwd {eb:.3e} <= {tol_b:.3e}")
+        assert ef <= tol_f and eb <= tol_b
+
+
+@pytest.mark.parametrize("bf16", [0, 1], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("shape,size,path", D.RESIZE_CL_CASES, ids=D.case_id)
+def test_resize_channels_last_per_element(L2d, shape, size, path, bf16):
+    """Every branch of mf_upsample_bilinear_cl_bwd (and the forward) per element; a ``tile`` shape runs the direct
+    kernel in fp32 (the tile kernel is bf16 only)."""
+    D.resize_cl_case(L2d, "cpu", _st, shape, size, bf16, path if bf16 or path != D.TILE else D.DIRECT, what="emul resize")
+
+
+@pytest.mark.parametrize("bf16", [0, 1], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("shape,size", D.RESIZE_CF_CASES, ids=D.case_id)
+def test_resize_channels_first_per_element(L2d, shape, size, bf16):
+    D.resize_cf_case(L2d, "cpu", _st, shape, size, bf16, what="emul resize cf")
+
+
+def test_resize_refusals(L2d):
+    D.resize_refusal_case(L2d, "cpu", _st)
+
+
+@pytest.mark.parametrize("bf16", [0, 1], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("n,slope", D.PRELU_CASES, ids=D.case_id)
+def test_prelu_backward_per_element(L2d, n, slope, bf16):
+    D.prelu_bwd_case(L2d, "cpu", _st, n, slope, bf16, what="emul prelu")
+
+
+@pytest.mark.parametrize("kw", D.BN_CASES, ids=D.case_id)
+def test_batchnorm_branches_per_element(L2d, kw):
+    D.bn_case(L2d, "cpu", _st, what="emul bn", **kw)

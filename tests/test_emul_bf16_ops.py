@@ -8,6 +8,7 @@ import torch.nn.functional as F
 
 import bf16_bound as BB
 import bf16_cases as C
+import decoder2d_cases as C2D
 from host_emul import emul
 
 pytestmark = pytest.mark.skipif(not emul.available(), reason="g++ not available")
@@ -473,3 +474,12 @@ def test_sampled_pspnet_tail_training_rows_vs_torch_formulation(monkeypatch):
         for k, v in got.items():
             assert v.shape == dict(net.named_parameters())[k].shape
             assert err(v, dict(net.named_parameters())[k].grad) < tol, (slope, k)
+
+
+@pytest.mark.parametrize("H,W", C2D.TAIL_MAPS)
+def test_tail_rows_kernels_per_element(H, W):
+    """mf_psp_tail_rows_bf16_fwd / _bwd called directly (tests/decoder2d_cases.py): forward rows bit-equal to the
+    float32 formulation, the backward -- LDS patch sums + fp32 atomics + one rounding -- per element against the exact
+    transpose in float64, exact zeros where no sample window reaches."""
+    L = emul.build(["psp_tail.hip"])
+    C2D.tail_rows_case(L, "cpu", lambda: None, H, W, what="emul tail rows")

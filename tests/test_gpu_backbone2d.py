@@ -120,3 +120,65 @@ def test_resnet18_extractor_inference_runs_on_the_fused_batchnorm_launch(monkeyp
         b = net(rgb.permute(0, 3, 1, 2))
         assert len(calls) == 20
     assert float((a - b).abs().max()) <= 1e-5 * float(b.abs().max())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Per element against float64 references under the derived bound (tests/decoder2d_ref.py, tests/decoder2d_cases.py --
+# the cases the emulator runs in tests/test_emul_backbone2d.py / test_emul_bf16_ops.py, here on the MI355X), each
+# asserting through mf_backbone2d_last_path() that the branch it was written for ran:
+#
+#     resize backward   direct / tile (bf16) / small     test_resize_channels_last_per_element
+#     BatchNorm         generic (C = 24, misaligned parameters, NCHW), per group G = 1 / 2 / 256 with ppt = 1
+#                                                        test_batchnorm_branches_per_element
+#                       per group, ppt = 2 and ppt = 4   test_batchnorm_pixels_per_lane_2_and_4
+import decoder2d_cases as D  # noqa: E402
+
+import morefusion_amd as mf  # noqa: E402
+
+
+@pytest.fixture()
+def L2d():
+    return mf._lib.lib()
+
+
+def _st():
+    return mf._lib.stream_ptr()
+
+
+@pytest.mark.parametrize("bf16", [0, 1], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("shape,size,path", D.RESIZE_CL_CASES, ids=D.case_id)
+def test_resize_channels_last_per_element(L2d, shape, size, path, bf16):
+    D.resize_cl_case(L2d, "cuda", _st, shape, size, bf16, path if bf16 or path != D.TILE else D.DIRECT, what="gpu resize")
+
+
+@pytest.mark.parametrize("bf16", [0, 1], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("shape,size", D.RESIZE_CF_CASES, ids=D.case_id)
+def test_resize_channels_first_per_element(L2d, shape, size, bf16):
+    D.resize_cf_case(L2d, "cuda", _st, shape, size, bf16, what="gpu resize cf")
+
+
+def test_resize_refusals(L2d):
+    D.resize_refusal_case(L2d, "cuda", _st)
+
+
+@pytest.mark.parametrize("bf16", [0, 1], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("n,slope", D.PRELU_CASES, ids=D.case_id)
+def test_prelu_backward_per_element(L2d, n, slope, bf16):
+    D.prelu_bwd_case(L2d, "cuda", _st, n, slope, bf16, what="gpu prelu")
+
+
+@pytest.mark.parametrize("kw", D.BN_CASES, ids=D.case_id)
+def test_batchnorm_branches_per_element(L2d, kw):
+    D.bn_case(L2d, "cuda", _st, what="gpu bn", **kw)
+
+
+@pytest.mark.parametrize("kw", D.BN_PPT_CASES, ids=D.case_id)
+def test_batchnorm_pixels_per_lane_2_and_4(L2d, kw):
+    """k_bn_act_cl at G = 256 with 2 and 4 pixels per lane (ResNet's first stage takes ppt = 2 in production): 4096
+    pixels is the launcher's threshold for ppt = 2; 8193 (threshold 8192) leaves the last workgroup ragged."""
+    D.bn_case(L2d, "cuda", _st, what="gpu bn", **kw)
+
+
+@pytest.mark.parametrize("H,W", D.TAIL_MAPS, ids=D.case_id)
+def test_tail_rows_kernels_per_element(L2d, H, W):
+    D.tail_rows_case(L2d, "cuda", _st, H, W, what="gpu tail rows")
