@@ -574,6 +574,14 @@ int mf_upsample_bilinear_cl_split_fwd(const float *x, void *y, int32_t B, int32_
                                       int32_t C, int32_t ldy, int32_t los, mfStream_t stream);
 int mf_split_bf16(const float *x, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int32_t B, int32_t C, int32_t H,
                   int32_t W, void *y, int32_t ldy, int32_t los, mfStream_t stream);
+/* PSPUpsample (x2 resize -> 3 x 3 convolution) with the convolution taken first: z fp32 [B, H, W, 9 C]
+ * holds the nine per-tap 1 x 1 convolutions of the low-resolution map (column t C + c, t = ky 3 + kx); output pixel p of
+ * the [B, 2H, 2W] map is v = act(bias + sum over the taps whose position p + (ky - 1, kx - 1) lies inside the map of
+ * bilinear(z_t) there), in increasing t, fp32.  v goes to y32[m * ld32 + c] and / or, split, to ys[m * lds + c] (hi) and
+ * ys[m * lds + los + c] (lo); either may be null.  act: 0 none, 1 ReLU, 2 PReLU with *slope (device pointer). */
+int mf_upsample2x_tapsum_fwd(const float *z, const float *bias, const float *slope, int32_t act, float *y32,
+                             int32_t ld32, void *ys, int32_t lds, int32_t los, int32_t B, int32_t H, int32_t W, int32_t C,
+                             mfStream_t stream);
 int mf_upsample_bilinear_cl_bwd(const void *gy, void *gx, int32_t B, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
                                 int32_t C, int32_t bf16, mfStream_t stream);
 /* ... and for channels-first tensors [B*C, H, W] (one lane per element) */

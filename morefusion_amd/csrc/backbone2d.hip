@@ -21,6 +21,18 @@ namespace {
 // torch's area_pixel_compute_scale / source index for align_corners = true, in float
 __device__ __forceinline__ float up_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.0f; }
 
+// Source taps of output pixel (oy, ox) of an align_corners resize [H][W] -> [Ho][Wo]: rows y0 / y0 + yp with weights
+// h0 / h1, columns x0 / x0 + xp with weights w0 / w1 (torch's arithmetic, in float)
+struct UpSrc { int y0, x0, yp, xp; float h0, h1, w0, w1; };
+__device__ __forceinline__ UpSrc up_src(int oy, int ox, int H, int W, int Ho, int Wo) {
+  UpSrc s;
+  const float sy = up_scale(H, Ho) * (float)oy, sx = up_scale(W, Wo) * (float)ox;
+  s.y0 = (int)sy; s.x0 = (int)sx;
+  s.yp = s.y0 < H - 1 ? 1 : 0; s.xp = s.x0 < W - 1 ? 1 : 0;
+  s.h1 = sy - (float)s.y0; s.h0 = 1.0f - s.h1; s.w1 = sx - (float)s.x0; s.w0 = 1.0f - s.w1;
+  return s;
+}
+
 template <bool BF16>
 __device__ __forceinline__ void load8(const void *p, int64_t idx, float v[8]) {
   if (BF16) {
@@ -58,12 +70,11 @@ __global__ __launch_bounds__(256) void k_up_fwd(const void *__restrict__ x, void
   const int c8 = (int)(i % C8);
   const int64_t pix = i / C8;
   const int ox = (int)(pix % Wo), oy = (int)((pix / Wo) % Ho), b = (int)(pix / ((int64_t)Wo * Ho));
-  const float sy = up_scale(H, Ho) * (float)oy, sx = up_scale(W, Wo) * (float)ox;
-  const int y0 = (int)sy, x0 = (int)sx;
-  const int yp = y0 < H - 1 ? 1 : 0, xp = x0 < W - 1 ? 1 : 0;
-  const float h1 = sy - (float)y0, h0 = 1.0f - h1, w1 = sx - (float)x0, w0 = 1.0f - w1;
+  const UpSrc s = up_src(oy, ox, H, W, Ho, Wo);
+  const int yp = s.yp, xp = s.xp;
+  const float h0 = s.h0, h1 = s.h1, w0 = s.w0, w1 = s.w1;
   const int C = 8 * C8;
-  const int64_t base = (((int64_t)b * H + y0) * W + x0) * C + 8 * c8;
+  const int64_t base = (((int64_t)b * H + s.y0) * W + s.x0) * C + 8 * c8;
   float a00[8], a01[8], a10[8], a11[8], o[8];
   load8<BF16>(x, base, a00);
   load8<BF16>(x, base + (int64_t)xp * C, a01);
@@ -98,12 +109,11 @@ __global__ __launch_bounds__(256) void k_up_fwd_split(const float *__restrict__ 
   const int c8 = (int)(i % C8);
   const int64_t pix = i / C8;
   const int ox = (int)(pix % Wo), oy = (int)((pix / Wo) % Ho), b = (int)(pix / ((int64_t)Wo * Ho));
-  const float sy = up_scale(H, Ho) * (float)oy, sx = up_scale(W, Wo) * (float)ox;
-  const int y0 = (int)sy, x0 = (int)sx;
-  const int yp = y0 < H - 1 ? 1 : 0, xp = x0 < W - 1 ? 1 : 0;
-  const float h1 = sy - (float)y0, h0 = 1.0f - h1, w1 = sx - (float)x0, w0 = 1.0f - w1;
+  const UpSrc s = up_src(oy, ox, H, W, Ho, Wo);
+  const int yp = s.yp, xp = s.xp;
+  const float h0 = s.h0, h1 = s.h1, w0 = s.w0, w1 = s.w1;
   const int C = 8 * C8;
-  const int64_t base = (((int64_t)b * H + y0) * W + x0) * C + 8 * c8;
+  const int64_t base = (((int64_t)b * H + s.y0) * W + s.x0) * C + 8 * c8;
   float a00[8], a01[8], a10[8], a11[8], o[8];
   load8<false>(x, base, a00);
   load8<false>(x, base + (int64_t)xp * C, a01);
@@ -112,6 +122,64 @@ __global__ __launch_bounds__(256) void k_up_fwd_split(const float *__restrict__ 
 #pragma unroll
   for (int k = 0; k < 8; ++k) o[k] = h0 * (w0 * a00[k] + w1 * a01[k]) + h1 * (w0 * a10[k] + w1 * a11[k]);
   store8_split(y, pix * ldy + 8 * c8, los, o);
+}
+
+// The x2 resize + 3 x 3 convolution of PSPUpsample with the convolution taken first: z [B][H][W][9 C]
+// fp32 holds the nine per-tap 1 x 1 convolutions z_t = W_t x of the LOW-resolution map (column t C + c, t = ky 3 + kx).
+// Output pixel p = (oy, ox) of the [2H][2W] map, channel c:
+//   v = act(bias[c] + sum over t = 0 .. 8 with q = p + (ky - 1, kx - 1) inside the map of bilinear(z_t)(q))
+// -- a tap that leaves the up-sampled map is the convolution's zero padding.  The bilinear term is k_up_fwd's
+// (same source arithmetic, same order of its four products), the taps are added in increasing t, all in fp32.  A lane
+// takes one pixel x 8 channels; v goes to y32 (pitch ld32) and / or to the split rows ys (pitch lds, lo plane at los).
+__global__ __launch_bounds__(256) void k_up_tapsum(const float *__restrict__ z, const float *__restrict__ bias,
+                                                   const float *__restrict__ slope, int act, float *__restrict__ y32,
+                                                   int ld32, uint16_t *__restrict__ ys, int lds, int los, int B, int H,
+                                                   int W, int C8) {
+  const int G = gridDim.x;
+  int64_t blk = blockIdx.x;
+  // XCD-contiguous logical order (as k_gemm_nt_bf16): an XCD's workgroups walk neighbouring output rows, so the z rows
+  // they share (each is read by ~6 output rows) are fetched into that XCD's L2 once
+  if ((G & 7) == 0) blk = (int64_t)(blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
+  const int64_t i = blk * blockDim.x + threadIdx.x;
+  const int Ho = 2 * H, Wo = 2 * W;
+  if (i >= (int64_t)B * Ho * Wo * C8) return;
+  const int c8 = (int)(i % C8);
+  const int64_t pix = i / C8;
+  const int ox = (int)(pix % Wo), oy = (int)((pix / Wo) % Ho), b = (int)(pix / ((int64_t)Wo * Ho));
+  const int C = 8 * C8;
+  const int64_t ldz = 9 * (int64_t)C;
+  const float *zb = z + (int64_t)b * H * W * ldz + 8 * c8;
+  float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky) {
+    const int qy = oy + ky - 1;
+    if (qy < 0 || qy >= Ho) continue;
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      const int qx = ox + kx - 1;
+      if (qx < 0 || qx >= Wo) continue;
+      const UpSrc s = up_src(qy, qx, H, W, Ho, Wo);
+      const float *p = zb + ((int64_t)s.y0 * W + s.x0) * ldz + (ky * 3 + kx) * C;
+      float a00[8], a01[8], a10[8], a11[8];
+      load8<false>(p, 0, a00);
+      load8<false>(p, s.xp * ldz, a01);
+      load8<false>(p, s.yp * W * ldz, a10);
+      load8<false>(p, ((int64_t)s.yp * W + s.xp) * ldz, a11);
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        acc[k] += s.h0 * (s.w0 * a00[k] + s.w1 * a01[k]) + s.h1 * (s.w0 * a10[k] + s.w1 * a11[k]);
+    }
+  }
+  float bv[8];
+  load8<false>(bias, 8 * c8, bv);
+  const float sl = act == 2 ? *slope : 0.0f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    acc[k] += bv[k];
+    if (act) acc[k] = acc[k] > 0.0f ? acc[k] : sl * acc[k];
+  }
+  if (y32) store8<false>(y32, pix * ld32 + 8 * c8, acc);
+  if (ys) store8_split(ys, pix * lds + 8 * c8, los, acc);
 }
 
 // x [B][C][H][W] fp32 at any element strides (channels-first or channels-last) -> the split form y [B][H][W] rows of
@@ -527,6 +595,29 @@ extern "C" int mf_upsample_bilinear_cl_split_fwd(const float *x, void *y, int32_
   hipLaunchKernelGGL(k_up_fwd_split, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x, (uint16_t *)y, B, H,
                      W, Ho, Wo, C / 8, ldy, los);
   return mf::check_launch("mf_upsample_bilinear_cl_split_fwd");
+}
+
+/* PSPUpsample's resize + 3 x 3 convolution from the per-tap 1 x 1 convolutions of the low-resolution map (k_up_tapsum):
+ * z fp32 [B, H, W, 9 C] (column t C + c, t = ky 3 + kx) -> v = act(bias + sum of the in-map taps' bilinear terms) on the
+ * [B, 2H, 2W] map, written as y32[m * ld32 + c] and / or ys[m * lds + c] = hi(v), ys[m * lds + los + c] = lo(v).
+ * act: 0 none, 1 ReLU, 2 PReLU with the single slope *slope (read on the device).  C and the pitches % 8 == 0, 16-byte
+ * aligned; fixed summation order, no atomics. */
+extern "C" int mf_upsample2x_tapsum_fwd(const float *z, const float *bias, const float *slope, int32_t act, float *y32,
+                                        int32_t ld32, void *ys, int32_t lds, int32_t los, int32_t B, int32_t H, int32_t W,
+                                        int32_t C, mfStream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if ((int64_t)B * H * W * C == 0) return 0;
+  if (C < 8 || C % 8 || H < 1 || W < 1 || B < 0 || !bias || (!y32 && !ys) || act < 0 || act > 2 || (act == 2 && !slope))
+    return bad2d("upsample2x_tapsum: C % 8 == 0, a bias, at least one output, act 0 / 1 / 2 (PReLU needs its slope)");
+  if ((y32 && (ld32 < C || ld32 % 8)) || (ys && (lds % 8 || los % 8 || los < C || lds < los + C)))
+    return bad2d("upsample2x_tapsum: pitches >= C and multiples of 8; lo plane inside the row");
+  if (((uintptr_t)z | (uintptr_t)bias | (uintptr_t)y32 | (uintptr_t)ys) & 15 || ((uintptr_t)slope & 3))
+    return bad2d("upsample2x_tapsum: 16-byte aligned operands");
+  const int64_t total = (int64_t)B * 4 * H * W * (C / 8);
+  if ((total + 255) / 256 >= (1ll << 31)) return bad2d("upsample2x_tapsum: too many output elements for one launch");
+  hipLaunchKernelGGL(k_up_tapsum, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, z, bias, slope, act, y32,
+                     ld32, (uint16_t *)ys, lds, los, B, H, W, C / 8);
+  return mf::check_launch("mf_upsample2x_tapsum_fwd");
 }
 
 /* fp32 x [B, C, H, W] at element strides (sb, sc, sh, sw) -> its split form y [B, H, W] rows of pitch ldy: hi at

@@ -15,6 +15,14 @@ PReLU and both output forms are the GEMM's epilogue.  Everything else (conv1, re
 pooled-branch 1x1 convolutions, training, autocast) stays on MIOpen, and so do res4 / res5 / up2
 below SPLIT_MIN_BATCH objects (the dispatch table).  ``split_bf16 = False``
 on ``ResNet18`` / ``PSPNetExtractor`` switches the path off (A/B runs).
+
+On that path up1 and up2 take their 3x3 convolution BEFORE the x2 resize: nothing
+non-linear sits between the two, so conv3x3(U x)(p) = bias + sum_t m_t(p) (U (W_t x))(p + d_t).
+The nine taps W_t are one 1x1 split-bf16 GEMM Cin -> 9 Cout on the low-resolution map (a quarter
+of the pixels), and csrc/backbone2d.hip's tap-sum resize (mf_upsample2x_tapsum_fwd) adds each
+tap's up-sampled map at its offset, masks the taps that leave the map, and applies bias + PReLU.
+``PSPNetExtractor.conv_before_resize = False`` restores resize -> 3x3 GEMM (A/B runs);
+CONV_BEFORE_RESIZE_MIN_BATCH is its dispatch table.
 """
 
 import os
@@ -54,6 +62,11 @@ class ResBlock(nn.Sequential):
 # times at 1 and 8 objects (tools/time_conv2d_split.py).  At one object res4 / res5 / up2 have too few
 # output tiles for the GEMM (32-64 workgroups on 256 CUs) and MIOpen is faster; up1 is 2x faster split at any batch.
 SPLIT_MIN_BATCH = {"res4_res5": 4, "psp_up1": 1, "up2": 4}
+# Dispatch of the conv-before-resize form of the decoder's up-sampling blocks: the smallest batch at
+# which a block runs as tap GEMM at the low resolution + tap-sum resize instead of resize + 3 x 3 convolution.  The
+# per-layer times at 1 and 8 objects (tools/time_psp_conv_before_resize.py) have NOT been taken yet: 4 follows
+# SPLIT_MIN_BATCH's threshold, where the 4x fewer MFMA FLOPs decide, and one object keeps its launches as they were.
+CONV_BEFORE_RESIZE_MIN_BATCH = {"up1": 4, "up2": 4}
 
 
 def _split_path(module, x, group):
@@ -316,6 +329,12 @@ class PSPNetExtractor(nn.Module):
 
     bf16_tail_kernels = True  # the sampled tail under bf16 autocast on the hand-written kernels (_tail_rows_bf16)
     split_bf16 = True  # psp.bottleneck, up1.conv, up2.conv as split-bf16 GEMMs in fp32 inference (module docstring)
+    # up1 / up2 of the split path: convolution at the low resolution, then the resize; MF_CONV_BEFORE_RESIZE=0
+    # starts a process with the switch off (A/B runs of bench.py)
+    conv_before_resize = os.environ.get("MF_CONV_BEFORE_RESIZE", "1") != "0"
+
+    def _conv_first(self, x, layer):
+        return self.conv_before_resize and x.shape[0] >= CONV_BEFORE_RESIZE_MIN_BATCH[layer]
 
     def __getstate__(self):  # the tail kernel's packed weights are a cache
         state = dict(self.__dict__)
@@ -373,12 +392,20 @@ class PSPNetExtractor(nn.Module):
         convolution and the log-softmax of the torch formulation (~55 launches) fused.  Inference, fp32, CUDA."""
         from .. import _lib
         if _split_path(self, x, "psp_up1") and self.up1.prelu.weight.numel() == 1:
-            h = self._psp_up1_split(x)  # fp32 [B, 2H, 2W, 256]
-            if _split_path(self, x, "up2") and self.up2.prelu.weight.numel() == 1:
+            slope2 = self.up2.prelu.weight.detach()
+            if slope2.numel() == 1 and self._conv_first(x, "up2"):
+                # up2's nine taps as one GEMM at up1's resolution: up1 hands over the split form only
+                _, hs = self._psp_up1_split(x, need32=False, needs=True)
+                z = ops2d.conv_taps_split(hs, self.up2.conv)
+                u2, _ = ops2d.upsample_tapsum(z, self.up2.conv.bias.detach(), act=2, slope=slope2)
+                u2 = u2.permute(0, 3, 1, 2)
+            elif slope2.numel() == 1 and _split_path(self, x, "up2"):
+                h, _ = self._psp_up1_split(x)  # fp32 [B, 2H, 2W, 256]
                 us = ops2d.upsample_split(h, 2 * h.shape[1], 2 * h.shape[2])
-                u2, _ = ops2d.conv_split(us, self.up2.conv, act=2, slope=self.up2.prelu.weight.detach())
+                u2, _ = ops2d.conv_split(us, self.up2.conv, act=2, slope=slope2)
                 u2 = u2.permute(0, 3, 1, 2)
             else:
+                h, _ = self._psp_up1_split(x)
                 u2 = self.up2(h.permute(0, 3, 1, 2))
         else:
             u2 = self.up2(self.up1(self.psp(x)))  # [B,64,H,W], H = W = 128; NCHW or channels-last strides, both read in place
@@ -406,11 +433,13 @@ class PSPNetExtractor(nn.Module):
             _lib.stream_ptr()), "mf_psp_tail_fwd")
         return out
 
-    def _psp_up1_split(self, x):
+    def _psp_up1_split(self, x, need32=True, needs=False):
         """``up1(psp(x))`` with the bottleneck and up1's convolution on split maps: the four up-sampled branches and x
         are written in split form straight into the concat map [B,H,W,2 * 5C] (hi channels of the concat, then its lo
         channels), the bottleneck (+ bias + ReLU) gives fp32 for the resize, the resize writes split form again and
-        up1.conv (+ bias + PReLU) gives fp32 [B,2H,2W,256] (channels-last)."""
+        up1.conv (+ bias + PReLU) gives (fp32 [B,2H,2W,256] channels-last, its split form [B,2H,2W,512]): only the
+        forms asked for, None for the other.  With ``conv_before_resize`` the bottleneck writes split form only,
+        up1's nine taps are one 1 x 1 GEMM on it at [H,W] and the tap-sum resize applies bias + PReLU."""
         psp = self.psp
         B, C, H, W = x.shape
         Ct = C * (len(psp.sizes) + 1)
@@ -419,10 +448,14 @@ class PSPNetExtractor(nn.Module):
             hb = conv(pooled).permute(0, 2, 3, 1).contiguous()
             ops2d.upsample_split(hb, H, W, out=cat, c_off=i * C, los=Ct)
         ops2d.to_split(x, out=cat, c_off=Ct - C, los=Ct)
+        slope = self.up1.prelu.weight.detach()
+        if self._conv_first(x, "up1"):
+            _, bs = ops2d.conv_split(cat, psp.bottleneck, act=1, out32=False, outs=True)
+            z = ops2d.conv_taps_split(bs, self.up1.conv)
+            return ops2d.upsample_tapsum(z, self.up1.conv.bias.detach(), act=2, slope=slope, out32=need32, outs=needs)
         b32, _ = ops2d.conv_split(cat, psp.bottleneck, act=1)
         us = ops2d.upsample_split(b32, 2 * H, 2 * W)
-        h, _ = ops2d.conv_split(us, self.up1.conv, act=2, slope=self.up1.prelu.weight.detach())
-        return h
+        return ops2d.conv_split(us, self.up1.conv, act=2, slope=slope, out32=need32, outs=needs)
 
     @staticmethod
     def _tail_taps(pix, H, W):

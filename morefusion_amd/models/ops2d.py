@@ -267,3 +267,66 @@ def conv_split(xs, conv, res=None, act=0, slope=None, out32=True, outs=False):
                                      _lib.ptr(ys), 2 * Cout, Cout, _lib.ptr(ws), nws, B, Cin, Cout, D, k, stride, pad, dil,
                                      _lib.stream_ptr()), "mf_conv2d_split_fwd")
     return y32, ys
+
+
+# ---- PSPUpsample with the convolution before the resize ----------------------------------------------
+# conv3x3(U x)(p) = bias + sum_t m_t(p) (U z_t)(p + d_t), z_t = W_t x: nothing non-linear sits between the resize U and
+# the convolution, so its nine taps are ONE 1 x 1 convolution Cin -> 9 Cout on the low-resolution map (a quarter of the
+# pixels: 4x fewer MFMA FLOPs), followed by a gather that resizes each tap's map at its own offset.
+
+def tap_pack(conv):
+    """``conv.weight`` [Cout, Cin, 3, 3] as the 1 x 1 convolution Cin -> 9 Cout (row t Cout + co, t = ky 3 + kx) in
+    ``split_pack``'s form, bf16 [9 Cout, 1, 3 Cin]; cached on the module the same way."""
+    w = conv.weight
+    key = (w.data_ptr(), w._version)
+    hit = conv.__dict__.get("_tap_pack")
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    Cout, Cin, k, k2 = w.shape
+    if k != 3 or k2 != 3:
+        raise ValueError("tap_pack: a 3 x 3 convolution is required")
+    wf = w.detach().float().permute(2, 3, 0, 1).reshape(9 * Cout, Cin).contiguous()
+    wp = torch.empty((9 * Cout, 1, 3 * Cin), dtype=torch.bfloat16, device=w.device)
+    _lib.check(_lib.lib().mf_conv2d_split_pack(wf.data_ptr(), 9 * Cout, Cin, 1, wp.data_ptr(), _lib.stream_ptr()),
+               "mf_conv2d_split_pack")
+    if not (w.is_cuda and torch.cuda.is_current_stream_capturing()):
+        conv.__dict__["_tap_pack"] = (key, wp)
+    return wp
+
+
+def conv_taps_split(xs, conv):
+    """The nine per-tap 1 x 1 convolutions of the split map xs [B, D, D, 2 Cin] with ``conv``'s 3 x 3 weights -> fp32
+    z [B, D, D, 9 Cout] (column t Cout + co); no bias, no activation: those follow the resize (``upsample_tapsum``)."""
+    B, D, D2, C2 = xs.shape
+    Cout, Cin = conv.weight.shape[:2]
+    if D2 != D or C2 != 2 * Cin or not xs.is_contiguous():
+        raise ValueError(f"conv_taps_split: a contiguous square split map [B, D, D, {2 * Cin}] is required, got {tuple(xs.shape)}")
+    if conv.stride[0] != 1 or conv.padding[0] != 1 or conv.dilation[0] != 1:
+        raise ValueError("conv_taps_split: stride 1, padding 1, dilation 1")
+    L = _lib.lib()
+    wp = tap_pack(conv)
+    N = 9 * Cout
+    z = torch.empty((B, D, D, N), dtype=torch.float32, device=xs.device)
+    nws = L.mf_conv2d_split_workspace_bytes(B, Cin, N, D, 1, 1, 0, 1)
+    ws = torch.empty((nws,), dtype=torch.uint8, device=xs.device) if nws > 0 else None
+    _lib.check(L.mf_conv2d_split_fwd(xs.data_ptr(), wp.data_ptr(), None, None, 0, None, 0, z.data_ptr(), N, None, 0, 0,
+                                     _lib.ptr(ws), nws, B, Cin, N, D, 1, 1, 0, 1, _lib.stream_ptr()),
+               "mf_conv2d_split_fwd")
+    return z
+
+
+def upsample_tapsum(z, bias, act=0, slope=None, out32=True, outs=False):
+    """act(bias + the sum over the in-map taps of the x2 bilinear resize (align_corners) of z's tap maps at the taps'
+    offsets): fp32 z [B, H, W, 9 C] -> (fp32 [B, 2H, 2W, C] or None, split [B, 2H, 2W, 2C] or None).  act as
+    ``conv_split``."""
+    B, H, W, N = z.shape
+    if N % 72 or z.dtype != torch.float32 or not z.is_contiguous():
+        raise ValueError(f"upsample_tapsum: contiguous fp32 [B, H, W, 9 C] with C % 8 == 0 is required, got {tuple(z.shape)}")
+    C = N // 9
+    _lib.require_gpu(z, bias)
+    y32 = torch.empty((B, 2 * H, 2 * W, C), dtype=torch.float32, device=z.device) if out32 else None
+    ys = torch.empty((B, 2 * H, 2 * W, 2 * C), dtype=torch.bfloat16, device=z.device) if outs else None
+    _lib.check(_lib.lib().mf_upsample2x_tapsum_fwd(z.data_ptr(), bias.data_ptr(), _lib.ptr(slope), act, _lib.ptr(y32), C,
+                                                   _lib.ptr(ys), 2 * C, C, B, H, W, C, _lib.stream_ptr()),
+               "mf_upsample2x_tapsum_fwd")
+    return y32, ys
