@@ -622,6 +622,25 @@ int mf_prelu_bwd(const void *x, const void *dy, const float *slope, void *dx, fl
  * environment forces never / wherever possible). */
 int mf_gemm_bf16_last_tile(void);
 
+/* The launch plans of the bf16 GEMM engines, answered by the very functions the launchers use (csrc/gemm_bf16.hip:
+ * nt_plan / tn_plan): host arithmetic over the problem and the MF_NT_BIG / MF_NT_SPLITK / MF_TN_PP / MF_NT_HALF_MAX
+ * knobs (read from the environment at every call), no device call.  Both return 0, or a negative code for a malformed
+ * question.
+ *   mf_gemm_bf16_nt_plan: C [M][N] per group over K.  ``mode`` 0 rows (mf_linear_bf16), 1 conv forward, 2 the k4 / s2
+ *     data gradient, 3 / 4 / 5 the split-bf16 2-D conv / 3-D conv / rows; ``table``: the rows come with a group table
+ *     (mf_linear_bf16_tiles); ``dgrad_rows``: (D/2)^3 of the data gradient, 0 otherwise; ``may_split``: the entry point
+ *     can split K (mf_conv3d_bf16_fwd_ws and the *_split_fwd) and ``have_ws``: it was given a workspace.
+ *     -> *tile = 64 / 128 / 256 rows, *S = splits of K (the *_workspace_bytes functions answer S * M * N * 4, 0 at S = 1).
+ *   mf_gemm_bf16_tn_plan: a weight gradient [Ni][Nj] at row pitch ldc, reduced over ``rows`` rows, ``groups`` side by
+ *     side; ``ranges``: mf_linear_wgrad_bf16_ranges; ``conv``: mf_conv3d_bf16_wgrad; ``split``: the caller's, <= 0 =
+ *     the default.  -> *form = 128 (the 128 x 128 tile) / 256 (the ping-pong form), *default_split = what
+ *     mf_*_wgrad_default_split answer, *finish = the pass that adds the slabs: 0 none, 1 k_wgrad_finish,
+ *     2 k_wgrad_finish_deep, 3 k_wgrad_finish_conv. */
+int mf_gemm_bf16_nt_plan(int32_t mode, int64_t M, int32_t N, int32_t K, int32_t groups, int32_t table,
+                         int64_t dgrad_rows, int32_t may_split, int32_t have_ws, int32_t *tile, int32_t *S);
+int mf_gemm_bf16_tn_plan(int32_t Ni, int32_t Nj, int32_t ldc, int64_t rows, int32_t groups, int32_t ranges,
+                         int32_t conv, int32_t split, int32_t *form, int32_t *default_split, int32_t *finish);
+
 /* PSPNet's sampled tail under bf16 training (pspnet.py:18-22,50-56 at model.py:222's pixels): the 3 x 3 windows of
  * the virtually x2 up-sampled map as GEMM rows [B * P, 576] bf16 (column c * 9 + ky * 3 + kx) from the channels-last
  * bf16 map u2 [B, H, W, 64], pix [B * P] flat indices into [2H, 2W]; and the backward: grows -> gu2 [B, H, W, 64] bf16

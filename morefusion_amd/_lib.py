@@ -176,6 +176,8 @@ _SIGNATURES = {
     "mf_prelu_bwd_workspace_floats": ([_i64], _i64),
     "mf_prelu_bwd": ([_p, _p, _p, _p, _p, _p, _i64, _i, _p], _i),
     "mf_gemm_bf16_last_tile": ([], _i),
+    "mf_gemm_bf16_nt_plan": ([_i, _i64, _i, _i, _i, _i, _i64, _i, _i, _p, _p], _i),
+    "mf_gemm_bf16_tn_plan": ([_i, _i, _i, _i64, _i, _i, _i, _i, _p, _p, _p], _i),
     "mf_psp_tail_rows_bf16_fwd": ([_p, _p, _i, _i, _i, _i, _p, _p], _i),
     "mf_psp_tail_rows_bf16_bwd": ([_p, _p, _i, _i, _i, _i, _p, _p, _p], _i),
     "mf_confidence_loss_fwd": ([_p, _p, _i, _i, _f, _p, _p, _p], _i),

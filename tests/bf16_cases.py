@@ -1,7 +1,10 @@
 """TEST INFRASTRUCTURE: the bodies of the bf16 engine cases (csrc/gemm_bf16.hip through the C ABI and bf16_ops),
 shared by the emulator tests (CPU tensors as device memory) and tests/test_gpu_bf16_branches.py (the MI355X).
 Every case compares EVERY output element with the float64 reference of tests/bf16_bound.py under its derived bound;
-nothing here knows which tile or kernel the launcher picks -- the callers assert that."""
+the cases do not know which tile or kernel the launcher picks -- the callers assert that, with the launchers' rules
+restated below (shared with tests/test_emul_gemm_bf16_plan.py, which holds them against the library's own answer)."""
+import ctypes
+
 import torch
 import torch.nn.functional as F
 
@@ -28,6 +31,90 @@ def rnd(gen, *shape, scale=1.0):
 
 def ok(code, L=None):
     assert code == 0, (code, L.mf_last_error_string().decode() if L is not None and hasattr(L, "mf_last_error_string") else "")
+
+
+# ------------------------------------------------- the launchers' rules, restated (csrc/gemm_bf16.hip: nt_plan, tn_plan)
+# ``big`` / ``forced`` / ``half_max`` / ``tn_pp``: the MF_NT_BIG / MF_NT_SPLITK / MF_NT_HALF_MAX / MF_TN_PP knobs (None,
+# 0, 255, None = not set).
+def nt_tile(M, N, groups=1, table=False, dgrad_rows=0, S=1, big=None, half_max=255):
+    """nt_plan's tile restated: the 256-row ping-pong form from 224 tiles of 256 x 256 on (N >= 160, no group table, a
+    data gradient only with 256 | Do^3) and for every split of K, else 64-row tiles up to 255 tiles of 128 x 128 (never
+    for the data gradient).  MF_NT_BIG: 0 never the 256-row form, 2 wherever its structure allows."""
+    full = -(-M // 128) * -(-N // 128) * groups
+    tiles = -(-M // 256) * -(-N // 256) * groups
+    can_big = not table and not (dgrad_rows and dgrad_rows % 256)
+    use_big = (tiles >= 224 and N >= 160 and can_big) or S > 1
+    if big == 2:
+        use_big = can_big
+    elif big is not None:
+        use_big = use_big and big == 1
+    if use_big:
+        return 256
+    return 64 if full <= half_max and not dgrad_rows else 128
+
+
+def nt_splitk(M, N, Kred, big=None, forced=0):
+    """nt_plan's split restated: 16 .. 159 tiles of 256 x 256 at N >= 192 split K over 256 / tiles workgroups, each >= 16
+    K-tiles of 64.  MF_NT_SPLITK forces a split that has a K-tile each; MF_NT_BIG=0 forbids the form a split runs on."""
+    if N < 192 or N % 8 or big == 0:
+        return 1
+    tiles, T = -(-M // 256) * -(-N // 256), -(-Kred // 64)
+    if forced > 0:
+        return forced if forced <= T else 1
+    if tiles >= 160 or tiles < 16:
+        return 1
+    S = 256 // tiles
+    while S > 1 and T // S < 16:
+        S -= 1
+    return S
+
+
+def tn_use_pp(Ni, Nj, rows, groups, ranges=False, big=None, tn_pp=None):
+    """tn_plan's form restated: results of >= 192 x 192 whose reduction leaves every workgroup of a chip-filling split
+    >= 48 K-tiles of 64 rows.  MF_TN_PP=0 / MF_NT_BIG=0: never; MF_NT_BIG=2: wherever there is no range table."""
+    if tn_pp == 0 or big == 0 or ranges:
+        return False
+    if big == 2:
+        return True
+    if Ni < 192 or Nj < 192:
+        return False
+    tiles = -(-Ni // 256) * -(-Nj // 256) * groups
+    fill = 1 if tiles >= 256 else -(-256 // tiles)
+    return -(-rows // 64) >= 48 * fill
+
+
+def deep_finish(split, slab_floats):
+    return split >= 32 and slab_floats <= 65536
+
+
+def wgrad_finish(split, slab_floats, conv=False):
+    """tn_plan's finish restated: 0 none (an unsplit linear result), 1 k_wgrad_finish, 2 k_wgrad_finish_deep,
+    3 k_wgrad_finish_conv (a convolution's slab of >= 2^20 floats)."""
+    if conv and slab_floats >= 1 << 20:
+        return 3
+    if not conv and split == 1:
+        return 0
+    return 2 if deep_finish(split, slab_floats) else 1
+
+
+# ... and the library's own answer (mf_gemm_bf16_nt_plan / mf_gemm_bf16_tn_plan: host arithmetic, no launch)
+MODE_ROWS, MODE_CONV, MODE_DGRAD, MODE_CONV2_SPLIT, MODE_CONV3_SPLIT, MODE_ROWS_SPLIT = range(6)
+
+
+def nt_plan(L, mode, M, N, K, groups=1, table=False, dgrad_rows=0, may_split=False, have_ws=False):
+    """-> (tile, S)"""
+    tile, S = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    ok(L.mf_gemm_bf16_nt_plan(mode, M, N, K, groups, int(table), dgrad_rows, int(may_split), int(have_ws),
+                              ctypes.byref(tile), ctypes.byref(S)), L)
+    return tile.value, S.value
+
+
+def tn_plan(L, Ni, Nj, rows, groups=1, ldc=None, ranges=False, conv=False, split=0):
+    """-> (form: 128 / 256, default split, finish kernel of ``split`` slabs: wgrad_finish's numbers)"""
+    form, dsplit, finish = ctypes.c_int32(-1), ctypes.c_int32(-1), ctypes.c_int32(-1)
+    ok(L.mf_gemm_bf16_tn_plan(Ni, Nj, Nj if ldc is None else ldc, rows, groups, int(ranges), int(conv), split,
+                              ctypes.byref(form), ctypes.byref(dsplit), ctypes.byref(finish)), L)
+    return form.value, dsplit.value, finish.value
 
 
 # ---------------------------------------------------------------------------------------------------------- NT rows

@@ -3,11 +3,13 @@ output element against the float64 CPU reference on the same bf16-rounded operan
 bound of tests/bf16_bound.py (no max-norm or percentage gates).  The case bodies are tests/bf16_cases.py, shared
 with the emulator tests.
 
-Which branch runs is read from outside where the library shows it -- ``mf_gemm_bf16_last_tile()`` (64 / 128 / 256-row
-NT tile), ``mf_conv3d_bf16_fwd_workspace_bytes`` (split-K and its S), ``mf_*_wgrad_default_split`` and the launcher's
-finish rule (deep: split >= 32 and a slab of <= 65536 floats), a call recorder on ``mf_conv3d_k3_narrow_bf16``.
-NOT observable from outside, restated here from the launchers instead: the TN engine's 128 x 128 against its
-ping-pong form (``tn_use_pp``) and the narrow kernel's tiles per wave -- the shapes sit on both sides of each rule.
+Which branch runs is read from outside where the library shows it -- ``mf_gemm_bf16_last_tile()`` (the 64 / 128 /
+256-row NT tile that RAN), ``mf_conv3d_bf16_fwd_workspace_bytes`` (split-K and its S), ``mf_*_wgrad_default_split``,
+``mf_gemm_bf16_tn_plan`` (the TN engine's 128 x 128 against its ping-pong form, and the finish kernel: plain, deep --
+split >= 32 and a slab of <= 65536 floats -- or the convolution's transpose), a call recorder on
+``mf_conv3d_k3_narrow_bf16``.  The launchers' rules are restated in tests/bf16_cases.py (held against the library's
+answers over every threshold by tests/test_emul_gemm_bf16_plan.py); the shapes here sit on both sides of each rule.
+NOT observable from outside, restated only: the narrow kernel's tiles per wave.
 
     branch                                   test                                              shape
     NT rows, 64-row tile                     test_linear_rows_tile_by_size[..64]               1000 x 136 x 200 x 3 groups; 300 x 24 x 8
@@ -53,42 +55,7 @@ def st():
     return mf._lib.stream_ptr()
 
 
-def nt_tile(M, N, groups=1, table=False, dgrad_rows=0):
-    """launch_nt restated: the 256-row ping-pong form from 224 tiles of 256 x 256 on (N >= 160, no group table, a data
-    gradient only with 256 | Do^3), else 64-row tiles up to 255 tiles of 128 x 128 (never for the data gradient)."""
-    full = -(-M // 128) * -(-N // 128) * groups
-    big = -(-M // 256) * -(-N // 256) * groups
-    if big >= 224 and N >= 160 and not table and not (dgrad_rows and dgrad_rows % 256):
-        return 256
-    return 64 if full <= 255 and not dgrad_rows else 128
-
-
-def nt_splitk(M, N, Kred):
-    """nt_splitk restated: 16 .. 159 tiles of 256 x 256 at N >= 192 split K over 256 / tiles workgroups, each >= 16
-    K-tiles of 64."""
-    if N < 192 or N % 8:
-        return 1
-    big, T = -(-M // 256) * -(-N // 256), -(-Kred // 64)
-    if big >= 160 or big < 16:
-        return 1
-    S = 256 // big
-    while S > 1 and T // S < 16:
-        S -= 1
-    return S
-
-
-def tn_use_pp(Ni, Nj, rows, groups):
-    """tn_use_pp restated: results of >= 192 x 192 whose reduction leaves every workgroup of a chip-filling split >= 48
-    K-tiles of 64 rows."""
-    if Ni < 192 or Nj < 192:
-        return False
-    tiles = -(-Ni // 256) * -(-Nj // 256) * groups
-    fill = 1 if tiles >= 256 else -(-256 // tiles)
-    return -(-rows // 64) >= 48 * fill
-
-
-def deep_finish(split, slab_floats):
-    return split >= 32 and slab_floats <= 65536
+nt_tile, nt_splitk, tn_use_pp, deep_finish = C.nt_tile, C.nt_splitk, C.tn_use_pp, C.deep_finish   # (the rules restated)
 
 
 # ---------------------------------------------------------------------------------------------------------- NT rows
@@ -158,6 +125,7 @@ def test_linear_wgrad_both_tn_forms(L, M, pp):
     assert tn_use_pp(N, Kc, M, 4) == pp
     split = int(L.mf_linear_wgrad_bf16_default_split(M, N, Kc, 4))
     assert split >= 1 and not deep_finish(split, 4 * N * Kc)     # (k_wgrad_finish)
+    assert C.tn_plan(L, N, Kc, M, 4) == (256 if pp else 128, split, C.wgrad_finish(split, 4 * N * Kc))   # (the library's answer)
     C.linear_wgrad_case(L, DEV, st, M, N, Kc, 4, splits=sorted({1, 3, split}), what=f"TN linear {'pp' if pp else '128'}")
 
 
@@ -167,6 +135,7 @@ def test_linear_wgrad_deep_finish_by_default_split(L):
     M, N, Kc = 65536, 64, 72
     split = int(L.mf_linear_wgrad_bf16_default_split(M, N, Kc, 1))
     assert deep_finish(split, N * Kc) and not deep_finish(31, N * Kc) and not tn_use_pp(N, Kc, M, 1)
+    assert C.tn_plan(L, N, Kc, M) == (128, split, 2) and C.tn_plan(L, N, Kc, M, split=31) == (128, split, 1)
     C.linear_wgrad_case(L, DEV, st, M, N, Kc, 1, splits=(31, split), what="TN linear deep finish")
 
 
@@ -177,6 +146,7 @@ def test_conv_wgrad_both_tn_forms(L, B, pp):
     Cin, Cout, D = 32, 512, 32
     assert tn_use_pp(Cout, 64 * Cin, B * 16 ** 3, 1) == pp
     split = int(L.mf_conv3d_bf16_wgrad_default_split(B, Cin, Cout, 16, 4))
+    assert C.tn_plan(L, Cout, 64 * Cin, B * 16 ** 3, conv=True) == (256 if pp else 128, split, 3)   # (k_wgrad_finish_conv)
     C.conv_case(L, DEV, st, B, Cin, Cout, D, (4, 2, 1, 1), splits=sorted({1, split}), expect_tile=256,
                 what=f"TN conv {'pp' if pp else '128'}")
 
@@ -189,6 +159,8 @@ def test_general_geometry(L, Cin, Cout, D, geom):
     slabs of four 8^3 outputs, k_wgrad_finish_deep) and, for the stride-1 layer on a power-of-two grid, the data
     gradient through the flipped operand."""
     assert deep_finish(32, Cout * geom[0] ** 3 * Cin) and not deep_finish(3, Cout * geom[0] ** 3 * Cin)
+    rows = 4 * C.BB.conv_out_size(D, *geom) ** 3
+    assert [C.tn_plan(L, Cout, geom[0] ** 3 * Cin, rows, conv=True, split=s)[2] for s in (1, 3, 32)] == [1, 1, 2]
     C.conv_case(L, DEV, st, 4, Cin, Cout, D, geom, splits=(1, 3, 32), ldo_pad=8, c_off=8, what=f"conv {geom} D{D}")
 
 
@@ -198,6 +170,7 @@ def test_conv_wgrad_deep_finish_by_default_split(L):
     B, Cin, Cout, D, geom = 2, 8, 16, 64, (3, 2, 1, 1)
     split = int(L.mf_conv3d_bf16_wgrad_default_split(B, Cin, Cout, 32, 3))
     assert deep_finish(split, Cout * 27 * Cin)
+    assert C.tn_plan(L, Cout, 27 * Cin, B * 32 ** 3, conv=True) == (128, split, 2)
     C.conv_case(L, DEV, st, B, Cin, Cout, D, geom, splits=(split,), what="conv wgrad deep finish by size")
 
 
