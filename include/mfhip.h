@@ -1003,6 +1003,32 @@ int mf_full_grids(const double *points, const int64_t *p_off, const double *T, c
                   const double *origin, int32_t n_examples, int64_t total_points, int32_t dim,
                   int32_t *target_full, int32_t *nontarget_full, mfStream_t stream);
 
+/* ---- picking order: occlusion counts, normals, grasp poses (contrib/picking_order.py, csrc/pickorder.hip) ----
+ * What ros/src/morefusion_ros/nodes/select_picking_order.py measures on N + 1 renders, on the renderer's own
+ * outputs: `instance` / `depth` [N + 1, height, width] with target 0 the composite of the N items and target 1 + n
+ * item n alone, item_id[n] the value item n writes (distinct, >= 0).  DESIGN.md "Picking order".  Every call is
+ * asynchronous, allocates nothing and never synchronises. */
+#define MF_PICK_MAX_OBJECTS 64 /* items of one call: N + 1 targets of 4096 x 4096 still fit MF_RENDER_MAX_PIXELS */
+/* whole[n]: pixels of item n alone.  occluded_by[i, j] ([N, N]): pixels that are i's alone and j's in the composite
+ * (the diagonal: i's visible pixels; a row sums to whole[i]).  bbox[n] = (min_row, min_col, max_row + 1,
+ * max_col + 1) of item n alone, zeros for no pixels.  All int32, cleared here. */
+int mf_pick_occlusion(const int32_t *instance, const int32_t *item_id, int32_t n_items, int32_t height,
+                      int32_t width, int32_t *whole, int32_t *occluded_by, int32_t *bbox, mfStream_t stream);
+/* geometry/estimate_pointcloud_normals.py _estimate_pointcloud_normals_organized for n_images images of float64
+ * points [n_images, height, width, 3], each inside its rectangle rect[t] = (y1, x1, y2, x2) (clipped to the image):
+ * the neighbours at offset 2 outside the RECTANGLE are NaN, as the reference pads a crop.  normals (same shape) is
+ * written completely, NaN outside the rectangle. */
+int mf_pick_normals(const double *points, const int32_t *rect, int32_t n_images, int32_t height, int32_t width,
+                    double *normals, mfStream_t stream);
+/* get_grasp_pose per item, one workgroup each: the box is cut into cells of S x S pixels, S = max(1, isqrt((h w) /
+ * 30)) (the seeding grid of the reference's SLIC, which is not run); cell[n] = the cell with mask pixels whose
+ * centroid is nearest the mean of the centroids (first on a tie, -1: no pixels); translation[n] = mean of the
+ * back-projected points (pointcloud_from_depth) over its mask pixels, normal[n] = mean of its normals (rectangle =
+ * bbox[n]) that are not NaN, NaN if none.  float64 sums in the fixed order of csrc/pickorder.hip's header. */
+int mf_pick_grasp(const float *depth, const int32_t *instance, const int32_t *item_id, const int32_t *bbox,
+                  int32_t n_items, int32_t height, int32_t width, double fx, double fy, double cx, double cy,
+                  int32_t *cell, double *translation, double *normal, mfStream_t stream);
+
 /* ---- training-time augmentation (datasets/augmentation.py, csrc/augment.hip) -----------------------
  * RGBDPoseEstimationDatasetReIndexedBase._augment_rgbd for n examples of S x S pixels (S a multiple of 8 in
  * 8..256) per call.  rgb uint8 [n, S, S, 3]; pcd float32 or float64 [n, S, S, 3] (pcd_is_f64), NaN invalid;

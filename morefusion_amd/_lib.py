@@ -219,6 +219,9 @@ _SIGNATURES = {
     "mf_render_raster": ([_p, _i64, _p], _i),
     "mf_render_resolve": ([_p, _i64, _p], _i),
     "mf_full_grids": ([_p] * 5 + [_i, _i64, _i, _p, _p, _p], _i),
+    "mf_pick_occlusion": ([_p, _p, _i, _i, _i, _p, _p, _p, _p], _i),
+    "mf_pick_normals": ([_p, _p, _i, _i, _i, _p, _p], _i),
+    "mf_pick_grasp": ([_p, _p, _p, _p, _i, _i, _i, _d, _d, _d, _d, _p, _p, _p, _p], _i),
     "mf_augment_workspace_bytes": ([_i, _i], _i64),
     "mf_augment_mask": ([_p, _p, _i, _p, _i, _i, _i64] + [_p] * 9, _i),
     "mf_augment_rgb": ([_p, _p, _i, _i, _p, _p, _p], _i),
