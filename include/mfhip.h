@@ -1029,6 +1029,24 @@ int mf_pick_grasp(const float *depth, const int32_t *instance, const int32_t *it
                   int32_t n_items, int32_t height, int32_t width, double fx, double fy, double cx, double cy,
                   int32_t *cell, double *translation, double *normal, mfStream_t stream);
 
+/* ---- pose metric: batched ADD / ADD-S in float64 (metrics/average_distance_device.py, csrc/posemetric.hip) ----
+ * metrics.average_distance (morefusion/metrics/average_distance.py) for n_items items in one call.  Item i is the
+ * cloud item_cloud[i] (its points: points[cloud_off[c] .. cloud_off[c + 1]), float64 [*, 3], all clouds concatenated;
+ * cloud_off int32 [n_clouds + 1]) under T1[i] and T2[i] (float64 [n_items, 4, 4], row-major):
+ *   add[i] = mean_j |T1 p_j - T2 p_j|,   add_s[i] = mean_j min_k |T1 p_j - T2 p_k|   (exact brute force),
+ * without the translations if `translate` is 0.  Items may share clouds; max_points is the longest cloud's length
+ * (a host value: it sizes the grid and the workspace).  The arithmetic and the order of every sum are fixed (the
+ * header of csrc/posemetric.hip, DESIGN.md "Pose metric"): a result depends on its own item alone.  An item whose
+ * cloud index is out of range, or whose cloud is empty or longer than max_points, gets NaN and touches nothing.
+ * Asynchronous on `stream`; allocates nothing and never synchronises.  < 0: n_items outside 0 .. 65535,
+ * n_clouds < 1 or max_points < 1. */
+/* Host-only: bytes of the workspace (the per-point distances of every item); < 0: bad sizes. */
+int64_t mf_average_distance_f64_workspace_bytes(int32_t n_items, int32_t max_points);
+int mf_average_distance_f64(const double *points, const int32_t *cloud_off, const int32_t *item_cloud,
+                            const double *T1, const double *T2, int32_t n_clouds, int32_t n_items,
+                            int32_t max_points, int32_t translate, double *add, double *add_s, void *workspace,
+                            mfStream_t stream);
+
 /* ---- training-time augmentation (datasets/augmentation.py, csrc/augment.hip) -----------------------
  * RGBDPoseEstimationDatasetReIndexedBase._augment_rgbd for n examples of S x S pixels (S a multiple of 8 in
  * 8..256) per call.  rgb uint8 [n, S, S, 3]; pcd float32 or float64 [n, S, S, 3] (pcd_is_f64), NaN invalid;

@@ -222,6 +222,8 @@ _SIGNATURES = {
     "mf_pick_occlusion": ([_p, _p, _i, _i, _i, _p, _p, _p, _p], _i),
     "mf_pick_normals": ([_p, _p, _i, _i, _i, _p, _p], _i),
     "mf_pick_grasp": ([_p, _p, _p, _p, _i, _i, _i, _d, _d, _d, _d, _p, _p, _p, _p], _i),
+    "mf_average_distance_f64_workspace_bytes": ([_i, _i], _i64),
+    "mf_average_distance_f64": ([_p] * 5 + [_i] * 4 + [_p] * 4, _i),
     "mf_augment_workspace_bytes": ([_i, _i], _i64),
     "mf_augment_mask": ([_p, _p, _i, _p, _i, _i, _i64] + [_p] * 9, _i),
     "mf_augment_rgb": ([_p, _p, _i, _i, _p, _p, _p], _i),

@@ -447,19 +447,34 @@ class Model(nn.Module):
 
     @torch.no_grad()
     def evaluate(self, *, class_id, quaternion_true, translation_true, quaternion_pred,
-                 translation_pred, per_instance=False):
+                 translation_pred, per_instance=False, on_device=False):
         """ADD / ADD-S of the given poses (model.py:325-375), returned as a dict of means.
 
         ``per_instance=True`` is the reference's evaluation-mode report: one
         ``{add,add_s,add_or_add_s}/{class_id:04d}/{uuid}`` entry per object, which
-        ``training.PoseEstimationEvaluator`` regroups per class for the AUC."""
-        T_true = functions_module.transformation_matrix(
-            quaternion_true.float(), translation_true.float()).cpu().numpy()
-        T_pred = functions_module.transformation_matrix(quaternion_pred, translation_pred).cpu().numpy()
+        ``training.PoseEstimationEvaluator`` regroups per class for the AUC.
+
+        ``on_device=True`` scores all objects in one launch of ``metrics.average_distance_device`` (float64, exact
+        nearest neighbours): the poses stay on the device and only the two [B] result vectors are copied back.  The
+        default is the host path, one object at a time through a k-d tree."""
+        T_true = functions_module.transformation_matrix(quaternion_true.float(), translation_true.float())
+        T_pred = functions_module.transformation_matrix(quaternion_pred, translation_pred)
+        cids = torch.as_tensor(class_id).tolist()
+        if on_device:
+            classes = sorted(set(cids))
+            all_add, all_add_s = metrics.average_distance_device(
+                [self._models.get_pcd(c) for c in classes], T_true, T_pred,
+                cloud_index=[classes.index(c) for c in cids], device=T_pred.device)
+            all_add, all_add_s = all_add.cpu().numpy(), all_add_s.cpu().numpy()
+        else:
+            T_true, T_pred = T_true.cpu().numpy(), T_pred.cpu().numpy()
         report = {}
         adds, add_ss, mixed = [], [], []
-        for i, cid in enumerate(torch.as_tensor(class_id).tolist()):
-            add, add_s = metrics.average_distance([self._models.get_pcd(cid)], [T_true[i]], [T_pred[i]])
+        for i, cid in enumerate(cids):
+            if on_device:
+                add, add_s = all_add[i:i + 1], all_add_s[i:i + 1]
+            else:
+                add, add_s = metrics.average_distance([self._models.get_pcd(cid)], [T_true[i]], [T_pred[i]])
             adds.append(add[0])
             add_ss.append(add_s[0])
             mixed.append(add_s[0] if cid in CLASS_IDS_SYMMETRIC else add[0])
