@@ -228,6 +228,18 @@ int mf_icc_refine(const mfIccBatch *batch, float *q, float *t, float *adam_m,
  * the default), 3 = k_icc_bin + k_icc_tile + k_icc_accum (any no-entry grid values).  Negative: invalid descriptor. */
 int mf_icc_iteration_launches(const mfIccBatch *batch);
 
+/* The launch plan of a batch, as the launchers above will use it (host arithmetic over the descriptor and the
+ * MF_ICC_GENERAL / MF_ICC_BIN_CAP environment; launches nothing, touches no device memory, the descriptor's pointers
+ * may be NULL).  Fills the first n of these slots and returns how many are defined (15):
+ *    0 single_pass             1 launches per iteration       2 kernel behind k_icc_bin: 0 k_icc_tile + k_icc_accum,
+ *    3 workspace bytes         4 n_tab (k_icc_bin's grid)       1 k_icc_fused, 2 k_icc_fused_big
+ *    5 nbins                   6 hmax                         7 dynamic LDS bytes of the fused kernel (0 on the
+ *    8 LDS bytes of k_icc_tile 9 LDS bytes of k_icc_accum       two-kernel path)
+ *   10 NB (k_icc_accum's blocks per object)                  11 xcd_order
+ *   12 bin_cap_force          13 uniform_ns                  14 rec_n (records of the bins)
+ * Negative: invalid descriptor, out == NULL or n <= 0. */
+int mf_icc_plan(const mfIccBatch *batch, int64_t *out, int32_t n);
+
 /* Measurement hook so that bench.py can time ONE kernel of an ICC iteration with HIP events:
  * stage 0 = (optional pose refresh from q, t if non-NULL) + empty the bins + k_icc_bin (pose ->
  * world points -> x-plane bins of voxel-frame records); stage 1 = k_icc_tile alone (bins ->
@@ -237,9 +249,9 @@ int mf_icc_iteration_launches(const mfIccBatch *batch);
 int mf_icc_launch_stage(const mfIccBatch *batch, const float *q, const float *t, void *ws,
                         int32_t stage, mfStream_t stream);
 
-/* Tuning aid: with MF_ICC_DEBUG=32 in the environment k_icc_bin / k_icc_tile / k_icc_accum record
- * wall_clock64() phase stamps per workgroup; this copies the first n 64-bit words of that
- * table to host memory (synchronous).  Not used by the product path. */
+/* Tuning aid (a `make ICC_DEBUG=1` build only): with MF_ICC_DEBUG=32 in the environment k_icc_bin / k_icc_tile /
+ * k_icc_accum / k_icc_fused record wall_clock64() phase stamps per workgroup; this copies the first n 64-bit words
+ * of that table to host memory (synchronous).  Not used by the product path. */
 int mf_icc_debug_stamps(unsigned long long *host_out, int n);
 
 /* ---- A13 conv3 of the pose network on sparse voxelized features -----------------

@@ -90,6 +90,7 @@ _SIGNATURES = {
     "mf_icp_refine": ([_p, _p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _i, _i, _f, _f, _p, _p, _p], _i),
     "mf_icc_workspace_bytes": ([ctypes.POINTER(IccBatch)], _i64),
     "mf_icc_iteration_launches": ([ctypes.POINTER(IccBatch)], _i),
+    "mf_icc_plan": ([ctypes.POINTER(IccBatch), _p, _i], _i),
     "mf_icc_launch_stage": ([ctypes.POINTER(IccBatch), _p, _p, _p, _i, _p], _i),
     "mf_icc_prepare": ([ctypes.POINTER(IccBatch), _p, _p], _i),
     "mf_icc_loss_grad": ([ctypes.POINTER(IccBatch), _p, _p, _p, _p, _p, _p, _p], _i),

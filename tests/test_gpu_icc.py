@@ -11,6 +11,8 @@ pytestmark = pytest.mark.gpu
 
 import morefusion_amd as mf  # noqa: E402
 
+import icc_cases as C  # noqa: E402
+
 
 def dev(x):
     return torch.as_tensor(np.ascontiguousarray(x)).cuda()
@@ -170,6 +172,10 @@ def test_icc_compact_bins_overflow_list_gives_the_same_bits(scene8, monkeypatch,
         losses, _ = link.refine(*args, n_iter=20, return_history=True)
         outs.append((torch.cat([link.quaternion.data, link.translation.data], 1).cpu().numpy(), losses.cpu().numpy()))
         sizes.append(link._scenes.ws.numel() if hasattr(link, "_scenes") else None)
+        # the plan of the library that ran: k_icc_bin + k_icc_fused, or k_icc_bin + k_icc_tile + k_icc_accum
+        plan = C.query(mf._lib.lib(), link._scenes.desc)
+        assert (plan["launches"], plan["variant"]) == ((3, C.TILE_ACCUM) if general else (2, C.FUSED)), plan
+        assert plan["bin_cap_force"] == int(cap or 0) and plan["ws_bytes"] == link._scenes.ws.numel()
     np.testing.assert_array_equal(outs[0][0], outs[1][0])
     np.testing.assert_array_equal(outs[0][1], outs[1][1])
     if sizes[0] is not None:

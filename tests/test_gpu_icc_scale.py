@@ -20,6 +20,8 @@ pytestmark = pytest.mark.gpu
 
 import morefusion_amd as mf  # noqa: E402
 
+import icc_cases as C  # noqa: E402
+
 
 def dev(x):
     return torch.as_tensor(np.ascontiguousarray(x)).cuda()
@@ -112,6 +114,8 @@ def test_scene_of_40_and_64_objects_vs_oracle(n_obj, single_pass):
     q0, t0 = _pose0([sc])
     batch = mf.contrib.IccScenes([_dict(sc)], sdf_offset=0.02, single_pass=single_pass)
     assert batch.desc.grid_ne_binary == int(single_pass) and batch.desc.max_scene_objects == n_obj
+    want = C.TILE_ACCUM if not single_pass else C.FUSED_BIG if n_obj > 64 else C.FUSED    # (96 objects: k_icc_fused_big)
+    assert C.query(mf._lib.lib(), batch.desc)["variant"] == want
     loss, gq, gt = batch.loss_grad(dev(q0), dev(t0))
     l_o, gq_o, gt_o, _ = OC.icc_loss_grad(*_args(sc), q0, t0, sdf_offset=0.02)
     np.testing.assert_allclose(float(loss[0]), l_o, rtol=2e-5, atol=1e-6)

@@ -14,7 +14,7 @@ s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True
 s.record()
 for _ in range(10): run()
 e.record(); torch.cuda.synchronize()
-print(f"MF_ICC_SX={os.environ.get('MF_ICC_SX')} scenes={args.scenes_per_gpu} icc ms/refine = {s.elapsed_time(e)/10:.3f}  us/iter = {s.elapsed_time(e)/10/args.icc_iters*1e3:.2f}")
+print(f"scenes={args.scenes_per_gpu} icc ms/refine = {s.elapsed_time(e)/10:.3f}  us/iter = {s.elapsed_time(e)/10/args.icc_iters*1e3:.2f}")
 # clock check: after a heavy GEMM warm-up
 import subprocess
 x = torch.randn(8192, 8192, device="cuda")

@@ -14,4 +14,4 @@ s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True
 s.record()
 for _ in range(20): run()
 e.record(); torch.cuda.synchronize()
-print(f"U={os.environ.get('MF_ICC_U')} SX={os.environ.get('MF_ICC_SX')} us/iter = {s.elapsed_time(e)/20/args.icc_iters*1e3:.2f}  pose checksum {float(wl.q.double().sum()+wl.t.double().sum()):.9f}")
+print(f"us/iter = {s.elapsed_time(e)/20/args.icc_iters*1e3:.2f}  pose checksum {float(wl.q.double().sum()+wl.t.double().sum()):.9f}")

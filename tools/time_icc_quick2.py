@@ -1,5 +1,7 @@
-"""ICC refine timing (us per iteration from the 100- vs 20-iteration difference), default path, for env-variable A/B runs."""
+"""ICC refine timing (us per iteration from the 100- vs 20-iteration difference), default path, for env-variable A/B runs.
+MF_ICC_DEBUG is read by a `make ICC_DEBUG=1` build only: libmfhip_dbg.so unless MF_LIBMFHIP names another one."""
 import os, sys
+os.environ.setdefault("MF_LIBMFHIP", "libmfhip_dbg.so")  # (before bench imports morefusion_amd: _lib reads it then)
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import Workload, parse  # noqa: E402

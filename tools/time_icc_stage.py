@@ -1,5 +1,7 @@
-"""One k_icc_fused launch on a prepared scene, timed per MF_ICC_DEBUG variant (valid inputs every time)."""
+"""One k_icc_fused launch on a prepared scene, timed per MF_ICC_DEBUG variant (valid inputs every time).
+MF_ICC_DEBUG is read by a `make ICC_DEBUG=1` build only: libmfhip_dbg.so unless MF_LIBMFHIP names another one."""
 import ctypes, os, sys
+os.environ.setdefault("MF_LIBMFHIP", "libmfhip_dbg.so")  # (before morefusion_amd is imported: _lib reads it then)
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import morefusion_amd as mf  # noqa: E402
