@@ -691,6 +691,36 @@ int mf_pose_epilogue(const float *heads_out, int64_t ldo, int32_t np4, const int
                      const float *pts, const float *origin, const float *pitch, int32_t B, int32_t P, int32_t n_fg,
                      float *rot, float *trans, float *conf, mfStream_t stream);
 
+/* ---- point-cloud baseline network (contrib/singleview_pcd, csrc/pcdnet.hip; DESIGN.md "Point-cloud baseline network")
+ * Inference of examples/ycb_video/singleview_pcd/contrib/models/model.py:69-155,299-330 on rows m = b * P + p.  The GEMM
+ * layers run on mf_linear_split_fwd / mf_linear_fwd, the pose epilogue on mf_pose_epilogue (pts = p - center, origin =
+ * center, pitch = 1: ((p - c) + c) + t); these are the point-wise kernels in between.  None allocates or synchronises;
+ * each returns a negative code without launching for B <= 0, P <= 0, B * P > INT32_MAX or a misaligned pitch.
+ *   mf_pcdnet_workspace_offsets  byte offsets of the MF_PCDNET_WS_BUFFERS activation buffers in one workspace (256-byte
+ *       aligned; offsets[MF_PCDNET_WS_BUFFERS] = the total), in the order pts fp32 [M][3], f1 bf16 [M][256], xs bf16
+ *       [M][768], h3 bf16 [M][1024], h4 fp32 [M][1024], pooled fp32 [B][1024], gbias fp32 [B][1920], y fp32 [M][1920],
+ *       h1 bf16 [M][3840], h2 bf16 [M][1536], h3h bf16 [M][768], o fp32 [M][3 np4] with np4 = 4 n_fg rounded up to 8;
+ *       returns the number of buffers, or -1 (also for n_fg outside 1 .. MF_PCDNET_MAX_FG)
+ *   mf_pcdnet_workspace_bytes    that total, or -1
+ *   mf_pcdnet_stem   x_rows fp32 [M][32] (the PSPNet tail's rows), pcd fp32 [B][HW][3], pix int64 [M] flat pixel of each
+ *       row, center fp32 [B][3] or null -> pts fp32 [M][3] = p - center (p without a center), feat1 = relu(conv1_rgb |
+ *       conv1_pcd) in split form: f1 rows of pitch ld1 (rgb hi at 0, lo at 64, pcd hi at 128, lo at 192) and xs rows of
+ *       pitch ldx (channel c hi at c, lo at losx + c; c < 64 rgb, 64 .. 127 pcd).  w_rgb [64][32], w_pcd [64][3].
+ *   mf_pcdnet_pool   pooled [B][C] = mean over the P rows of each object of h fp32 (row pitch ldh), C % 64 == 0, in a
+ *       fixed order (no atomics)
+ *   mf_pcdnet_bias_relu_split  out[m][2 G g + j] = hi, out[m][2 G g + G + j] = lo of relu(y[m][G g + j] +
+ *       gbias[m / P][G g + j]); y fp32 row pitch ldy, gbias [B][N], out bf16 row pitch ldo >= 2 N; G % 8 == 0, G | N */
+#define MF_PCDNET_WS_BUFFERS 12
+#define MF_PCDNET_MAX_FG 256
+int32_t mf_pcdnet_workspace_offsets(int32_t B, int32_t P, int32_t n_fg, int64_t *offsets);
+int64_t mf_pcdnet_workspace_bytes(int32_t B, int32_t P, int32_t n_fg);
+int mf_pcdnet_stem(const float *x_rows, const float *pcd, const int64_t *pix, const float *center, const float *w_rgb,
+                   const float *b_rgb, const float *w_pcd, const float *b_pcd, int32_t B, int32_t P, int32_t HW,
+                   float *pts, void *f1, int32_t ld1, void *xs, int32_t ldx, int32_t losx, mfStream_t stream);
+int mf_pcdnet_pool(const float *h, int64_t ldh, int32_t B, int32_t P, int32_t C, float *pooled, mfStream_t stream);
+int mf_pcdnet_bias_relu_split(const float *y, int64_t ldy, const float *gbias, int32_t B, int32_t P, int32_t N, int32_t G,
+                              void *out, int64_t ldo, mfStream_t stream);
+
 /* The last PSPNet level (up3: bilinear x2 + Convolution2D 3x3 64->64 + PReLU; conv1 1x1 64->32; log-softmax,
  *   morefusion/models/dense_fusion/pspnet.py:10-35,57-73) evaluated ONLY at the sampled pixels the pose network
  *   reads (contrib/singleview_3d/models/model.py:222), one launch:

@@ -229,6 +229,11 @@ _SIGNATURES = {
     "mf_augment_mask": ([_p, _p, _i, _p, _i, _i, _i64] + [_p] * 9, _i),
     "mf_augment_rgb": ([_p, _p, _i, _i, _p, _p, _p], _i),
     "mf_augment_pcd": ([_p, _i, _p, _i, _i, _i64, _p, _p], _i),
+    "mf_pcdnet_workspace_offsets": ([_i, _i, _i, _p], _i),
+    "mf_pcdnet_workspace_bytes": ([_i, _i, _i], _i64),
+    "mf_pcdnet_stem": ([_p] * 8 + [_i] * 3 + [_p, _p, _i, _p, _i, _i, _p], _i),
+    "mf_pcdnet_pool": ([_p, _i64, _i, _i, _i, _p, _p], _i),
+    "mf_pcdnet_bias_relu_split": ([_p, _i64, _p, _i, _i, _i, _i, _p, _i64, _p], _i),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -5,6 +5,7 @@ from .iterative_closest_point_link import IterativeClosestPointLink, icp_refine
 from .iterative_collision_check_link import IterativeCollisionCheckLink
 from .occupancy_registration import OccupancyRegistration, OccupancyRegistrationLink
 from . import singleview_3d
+from . import singleview_pcd
 from .multi_instance_octree_mapping import MultiInstanceOctreeMapping
 from .icp_registration import ICPRegistration, icp_registration_batch
 from .instance_tracking import InstanceTracker, render_instance_maps, track_instance_ids

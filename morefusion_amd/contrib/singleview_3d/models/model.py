@@ -29,6 +29,7 @@ from .... import geometry as geometry_module
 from .... import metrics
 from ....models import PSPNetExtractor, ResNet18, ResNet18Extractor
 from ....synthetic import CLASS_IDS_SYMMETRIC, CLASS_PITCH
+from ...point_selection import PointSelection
 from .sparse_conv import SparseVoxelConv3d
 from .volumetric_cl import ChannelsLastVolumetric
 
@@ -50,7 +51,7 @@ class PitchTableModels:
         return self._pcds[int(class_id)]
 
 
-class Model(nn.Module):
+class Model(PointSelection, nn.Module):
 
     _lambda_confidence = 0.015
     _n_point = 1000
@@ -177,48 +178,8 @@ class Model(nn.Module):
         from ....chainer_compat import link_xp
         return link_xp(self)
 
-    # ---- point selection (model.py:191-230) ---------------------------------------------
-    _eval_keep_cache = {}
-
-    def _keep_indices(self, n_point):
-        """The reference's subsample / pad of the n valid pixels (model.py:208-219).  In eval
-        mode it seeds a fresh ``RandomState(1234)`` per object, i.e. it is a pure function of
-        n: memoised, so the GPU does not idle behind a host-side MT19937 permutation."""
-        if n_point == 0:
-            raise ValueError("an example has no valid point")
-        if not self.training:
-            hit = Model._eval_keep_cache.get((n_point, self._n_point))
-            if hit is not None:
-                return hit
-        random_state = np.random.mtrand._rand if self.training else np.random.RandomState(1234)
-        if n_point >= self._n_point:
-            keep = random_state.permutation(n_point)[: self._n_point]
-        else:
-            keep = np.r_[np.arange(n_point),
-                         random_state.randint(0, n_point, self._n_point - n_point)]
-        keep = keep.astype(np.int64)
-        if not self.training and len(Model._eval_keep_cache) < 4096:
-            Model._eval_keep_cache[(n_point, self._n_point)] = keep
-        return keep
-
-    def _select_points(self, pcd):
-        """pcd [B,H,W,3] -> flat pixel indices [B,P]: the row-major list of the pixels without a
-        NaN coordinate (``where(mask)``, model.py:195) from one launch of ``mf_valid_pixel_order``,
-        then the reference's NumPy-RNG subsample / pad of it."""
-        B, HW = pcd.shape[0], pcd.shape[1] * pcd.shape[2]
-        _lib.require_gpu(pcd)
-        pcd = _lib.f32c(pcd)
-        order = torch.empty((B, HW), dtype=torch.int32, device=pcd.device)
-        counts = torch.empty((B,), dtype=torch.int32, device=pcd.device)
-        _lib.check(_lib.lib().mf_valid_pixel_order(pcd.data_ptr(), B, HW, order.data_ptr(), counts.data_ptr(),
-                                                   _lib.stream_ptr()), "mf_valid_pixel_order")
-        return self._subsample(order, counts.cpu().numpy())  # the one host sync (the RNG needs n_point)
-
-    def _subsample(self, order, counts):
-        """order [B,HW] (valid pixels first, row-major), counts [B] on the host -> [B,P] int64:
-        ``iy[keep], ix[keep]`` of model.py:207-220 as flat indices."""
-        keep = torch.from_numpy(np.stack([self._keep_indices(int(c)) for c in counts])).to(order.device)
-        return torch.gather(order, 1, keep).long()
+    # ---- point selection (model.py:191-230): ``_keep_indices``, ``_select_points``, ``_subsample`` of the shared
+    # mix-in (contrib/point_selection.py; the point-cloud baseline network selects its points the same way)
 
     def predict(self, *, class_id, rgb, pcd, pitch=None, origin=None, grid_nontarget_empty=None):
         B = rgb.shape[0]

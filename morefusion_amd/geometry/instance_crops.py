@@ -54,22 +54,31 @@ def instance_crops(rgb, depth, K, instance_label, instance_ids, image_size=256, 
                 n_valid=stats[:, 5])
 
 
+def valid_points_median(pcd):
+    """pcd [n,S,S,3] (NaN = invalid) -> [n,3]: the per-axis median of each object's valid points (NumPy semantics:
+    the mean of the two middle values); NaN for an object without a valid point."""
+    n = pcd.shape[0]
+    flat = pcd.reshape(n, -1, 3)
+    cnt = (~torch.isnan(flat).any(dim=2)).sum(dim=1)
+    srt = torch.sort(flat, dim=1).values  # NaN sorts last, per coordinate
+    lo = ((cnt - 1).clamp(min=0) // 2)[:, None, None].expand(n, 1, 3)
+    hi = (cnt // 2).clamp(max=flat.shape[1] - 1)[:, None, None].expand(n, 1, 3)
+    c = (0.5 * (srt.gather(1, lo) + srt.gather(1, hi)))[:, 0]
+    return torch.where((cnt > 0)[:, None], c, torch.full_like(c, float("nan")))
+
+
 def grid_origin(pcd, pitch, dim=32, center="median"):
     """pcd [n,S,S,3] (NaN = invalid), pitch [n] -> origin [n,3] of each object's dim^3 grid:
     nan-median (NumPy semantics: mean of the two middle values) or nan-mean of the points,
     minus (dim/2 - 0.5) * pitch.  Objects without any valid point give NaN."""
     n = pcd.shape[0]
-    flat = pcd.reshape(n, -1, 3)
-    valid = ~torch.isnan(flat).any(dim=2)
-    cnt = valid.sum(dim=1)
     if center == "mean":
+        flat = pcd.reshape(n, -1, 3)
+        valid = ~torch.isnan(flat).any(dim=2)
+        cnt = valid.sum(dim=1)
         c = torch.where(valid[..., None], flat, torch.zeros_like(flat)).sum(dim=1) / cnt[:, None]
     elif center == "median":
-        srt = torch.sort(flat, dim=1).values  # NaN sorts last, per coordinate
-        lo = ((cnt - 1).clamp(min=0) // 2)[:, None, None].expand(n, 1, 3)
-        hi = (cnt // 2).clamp(max=flat.shape[1] - 1)[:, None, None].expand(n, 1, 3)
-        c = (0.5 * (srt.gather(1, lo) + srt.gather(1, hi)))[:, 0]
-        c = torch.where((cnt > 0)[:, None], c, torch.full_like(c, float("nan")))
+        c = valid_points_median(pcd)
     else:
         raise ValueError("center must be 'median' or 'mean'")
     pitch = torch.as_tensor(pitch, dtype=pcd.dtype, device=pcd.device).reshape(n, 1)
