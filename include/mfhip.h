@@ -594,6 +594,11 @@ int mf_split_bf16(const float *x, int64_t sb, int64_t sc, int64_t sh, int64_t sw
 int mf_upsample2x_tapsum_fwd(const float *z, const float *bias, const float *slope, int32_t act, float *y32,
                              int32_t ld32, void *ys, int32_t lds, int32_t los, int32_t B, int32_t H, int32_t W, int32_t C,
                              mfStream_t stream);
+/* ResNet18's stem tail in fp32 inference: max_pool2d(3, 2, 1), padding -inf, of fp32 x [B, C, H, W] at
+ * element strides -> the pooled map channels-last in fp32, y32 [B, Ho, Wo, C], and / or in split form, ys [B, Ho, Wo, 2C]
+ * (hi at channel c, lo at C + c); Ho = (H - 1) / 2 + 1.  C % 8 == 0, outputs 16-byte aligned, either may be null. */
+int mf_maxpool3s2_split_fwd(const float *x, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int32_t B, int32_t C,
+                            int32_t H, int32_t W, float *y32, void *ys, mfStream_t stream);
 int mf_upsample_bilinear_cl_bwd(const void *gy, void *gx, int32_t B, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
                                 int32_t C, int32_t bf16, mfStream_t stream);
 /* ... and for channels-first tensors [B*C, H, W] (one lane per element) */

@@ -167,6 +167,7 @@ _SIGNATURES = {
     "mf_upsample_bilinear_cl_split_fwd": ([_p, _p] + [_i] * 8 + [_p], _i),
     "mf_upsample2x_tapsum_fwd": ([_p, _p, _p, _i, _p, _i, _p] + [_i] * 6 + [_p], _i),
     "mf_split_bf16": ([_p, _i64, _i64, _i64, _i64] + [_i] * 4 + [_p, _i, _i, _p], _i),
+    "mf_maxpool3s2_split_fwd": ([_p, _i64, _i64, _i64, _i64] + [_i] * 4 + [_p, _p, _p], _i),
     "mf_upsample_bilinear_cl_bwd": ([_p, _p] + [_i] * 7 + [_p], _i),
     "mf_upsample_bilinear_cf_fwd": ([_p, _p, _i64] + [_i] * 5 + [_p], _i),
     "mf_upsample_bilinear_cf_bwd": ([_p, _p, _i64] + [_i] * 5 + [_p], _i),

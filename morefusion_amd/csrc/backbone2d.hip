@@ -199,6 +199,59 @@ __global__ __launch_bounds__(256) void k_split_bf16(const float *__restrict__ x,
   store8_split(y, pix * ldy + 8 * c8, los, v);
 }
 
+// ResNet18's stem tail: max_pool2d(3, 2, 1) of x [B][C][H][W] fp32 at any element strides (what MIOpen left of conv1:
+// channels-first) -> the pooled map channels-last in fp32, y32 [B][Ho][Wo][C] (res2.0's identity shortcut), and in split
+// form, ys [B][Ho][Wo][2C] (res2.0's GEMM operand), both from the same value.  Padding is -inf: nothing clamps the
+// map in front of the pool, negative maxima are real.  A workgroup takes 16 output pixels of a row x 64 channels:
+// the 3 x 3 windows are read with the lanes along the source's unit stride (x for channels-first, c for channels-last),
+// turned through LDS, and written as whole channels-last rows.
+constexpr int kMpPix = 16, kMpCh = 64, kMpPitch = kMpCh + 1;
+
+__global__ __launch_bounds__(256) void k_maxpool3s2_split(const float *__restrict__ x, int64_t sb, int64_t sc, int64_t sh,
+                                                          int64_t sw, int C, int H, int W, int Ho, int Wo, int strips,
+                                                          float *__restrict__ y32, uint16_t *__restrict__ ys) {
+  __shared__ float s_t[kMpPix * kMpPitch];
+  const int strip = blockIdx.x % strips, oy = blockIdx.x / strips;
+  const int c0 = blockIdx.y * kMpCh, b = blockIdx.z;
+  const float *xb = x + b * sb;
+  for (int i = threadIdx.x; i < kMpPix * kMpCh; i += 256) {
+    int p, c;
+    if (sc == 1) { c = i % kMpCh; p = i / kMpCh; }
+    else { p = i % kMpPix; c = i / kMpPix; }
+    const int ox = strip * kMpPix + p;
+    float m = -INFINITY;
+    if (ox < Wo && c0 + c < C) {
+      const float *xc = xb + (c0 + c) * sc;
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+        const int iy = 2 * oy + ky - 1;
+        if (iy < 0 || iy >= H) continue;
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          const int ix = 2 * ox + kx - 1;
+          if (ix < 0 || ix >= W) continue;
+          const float v = xc[iy * sh + ix * sw];
+          if (v > m || v != v) m = v;  // (torch's update rule: a NaN wins)
+        }
+      }
+    }
+    s_t[p * kMpPitch + c] = m;
+  }
+  __syncthreads();
+  if (threadIdx.x < kMpPix * (kMpCh / 8)) {
+    const int c8 = threadIdx.x % (kMpCh / 8), p = threadIdx.x / (kMpCh / 8);
+    const int ox = strip * kMpPix + p, ch = c0 + 8 * c8;
+    if (ox < Wo && ch < C) {
+      float v[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = s_t[p * kMpPitch + 8 * c8 + k];
+      const int64_t pix = ((int64_t)b * Ho + oy) * Wo + ox;
+      if (y32) store8<false>(y32, pix * C + ch, v);
+      if (ys) store8_split(ys, pix * 2 * C + ch, C, v);
+    }
+  }
+}
+
 // gx [B][H][W][C] = sum over the output pixels whose footprint contains (iy, ix), increasing (oy, ox)
 template <bool BF16>
 __global__ __launch_bounds__(256) void k_up_bwd(const void *__restrict__ gy, void *__restrict__ gx, int B, int H, int W,
@@ -632,6 +685,22 @@ extern "C" int mf_split_bf16(const float *x, int64_t sb, int64_t sc, int64_t sh,
   hipLaunchKernelGGL(k_split_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x, sb, sc, sh, sw, B,
                      C / 8, H, W, (uint16_t *)y, ldy, los);
   return mf::check_launch("mf_split_bf16");
+}
+
+/* max_pool2d(3, 2, 1) (padding -inf) of fp32 x [B, C, H, W] at element strides (sb, sc, sh, sw) -> y32 [B, Ho, Wo, C]
+ * channels-last fp32 and / or its split form ys [B, Ho, Wo, 2C] (hi at channel c, lo at C + c), Ho = (H - 1) / 2 + 1.
+ * C % 8 == 0, outputs 16-byte aligned; either output may be null. */
+extern "C" int mf_maxpool3s2_split_fwd(const float *x, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int32_t B,
+                                       int32_t C, int32_t H, int32_t W, float *y32, void *ys, mfStream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if ((int64_t)B * C * H * W == 0) return 0;
+  if (B < 0 || B > 65535 || C < 8 || C % 8 || H < 1 || W < 1 || !x || (!y32 && !ys) ||
+      (((uintptr_t)y32 | (uintptr_t)ys) & 15))
+    return bad2d("maxpool3s2_split: C % 8 == 0, B <= 65535, at least one output, aligned outputs");
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, strips = (Wo + kMpPix - 1) / kMpPix;
+  hipLaunchKernelGGL(k_maxpool3s2_split, dim3((unsigned)(strips * Ho), (unsigned)((C + kMpCh - 1) / kMpCh), (unsigned)B),
+                     dim3(256), 0, stream, x, sb, sc, sh, sw, C, H, W, Ho, Wo, strips, y32, (uint16_t *)ys);
+  return mf::check_launch("mf_maxpool3s2_split_fwd");
 }
 
 extern "C" int mf_upsample_bilinear_cl_bwd(const void *gy, void *gx, int32_t B, int32_t H, int32_t W, int32_t Ho,

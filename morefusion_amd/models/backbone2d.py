@@ -4,17 +4,18 @@ Restates morefusion/models/dense_fusion/resnet.py:9-136 and pspnet.py:10-82 with
 ``torch.nn`` layers.  No BatchNorm anywhere (the reference has none); ``F.resize_images`` ==
 bilinear with align_corners=True; PReLU has one shared slope initialised to 0.25.
 
-Inference in fp32 (CUDA, eval mode, no grad, no autocast) runs the large convolutions -- res4,
-res5, psp.bottleneck, up1.conv and up2.conv, 98 % of the network's FLOPs -- as split-bf16 GEMMs
-on the MFMA engine of csrc/gemm_bf16.hip (mf_conv2d_split_fwd): every fp32 value
-x is carried as hi = bf16(x), lo = bf16(x - hi) and a product x w as hi w_hi + lo w_hi + hi w_lo,
-accumulated in fp32.  Per product that differs from x w by at most ~3 * 2^-18 relative (the
-split leaves <= 2^-18 |x|, the dropped lo lo term <= 2^-18 |x w|): ~40x tighter than TF32, not
-bit-equal to MIOpen.  Maps stay in split form between the convolutions; bias, residual, ReLU /
-PReLU and both output forms are the GEMM's epilogue.  Everything else (conv1, res2, res3, the
-pooled-branch 1x1 convolutions, training, autocast) stays on MIOpen, and so do res4 / res5 / up2
-below SPLIT_MIN_BATCH objects (the dispatch table).  ``split_bf16 = False``
-on ``ResNet18`` / ``PSPNetExtractor`` switches the path off (A/B runs).
+Inference in fp32 (CUDA, eval mode, no grad, no autocast) runs the convolutions behind conv1 -- res2 .. res5,
+psp.bottleneck, up1.conv and up2.conv -- as split-bf16 GEMMs on the MFMA engine of csrc/gemm_bf16.hip
+(mf_conv2d_split_fwd): every fp32 value x is carried as hi = bf16(x), lo = bf16(x - hi) and a product
+x w as hi w_hi + lo w_hi + hi w_lo, accumulated in fp32.  Per product that differs from x w by at most ~3 * 2^-18
+relative (the split leaves <= 2^-18 |x|, the dropped lo lo term <= 2^-18 |x w|): ~40x tighter than TF32, not bit-equal
+to MIOpen.  Maps stay in split form between the convolutions; bias, residual, ReLU / PReLU and both output forms are
+the GEMM's epilogue.  The stem's max-pool reads conv1's output where MIOpen left it and writes res2.0's two operands
+(fp32 channels-last for the identity shortcut, split form for the GEMMs) in one launch (mf_maxpool3s2_split_fwd).
+conv1 itself (Cin = 3), the pooled-branch 1x1 convolutions, training and autocast stay on MIOpen, and so does every
+layer group below its SPLIT_MIN_BATCH objects (the dispatch table) and any map that is not square with a power-of-two
+side.  ``split_bf16 = False`` on ``ResNet18`` / ``PSPNetExtractor`` switches the path off; ``ResNet18.front_split``
+switches the front end (pool, res2, res3) alone (A/B runs).
 
 On that path up1 and up2 take their 3x3 convolution BEFORE the x2 resize: nothing
 non-linear sits between the two, so conv3x3(U x)(p) = bias + sum_t m_t(p) (U (W_t x))(p + d_t).
@@ -61,7 +62,10 @@ class ResBlock(nn.Sequential):
 # Dispatch of the split-bf16 path: the smallest batch at which a layer group runs it instead of MIOpen, from per-layer
 # times at 1 and 8 objects (tools/time_conv2d_split.py).  At one object res4 / res5 / up2 have too few
 # output tiles for the GEMM (32-64 workgroups on 256 CUs) and MIOpen is faster; up1 is 2x faster split at any batch.
-SPLIT_MIN_BATCH = {"res4_res5": 4, "psp_up1": 1, "up2": 4}
+# res2_res3 (the stem's pool + res2 + res3, tools/time_conv2d_split.py --front at 1, 4, 8 objects): summed over a
+# predict's calls the layers are 0.03 ms faster split at four objects and 0.01 ms slower at one, and ~24 glue launches
+# go; one object keeps its launches.
+SPLIT_MIN_BATCH = {"res4_res5": 4, "psp_up1": 1, "up2": 4, "res2_res3": 4}
 # Dispatch of the conv-before-resize form of the decoder's up-sampling blocks: the smallest batch at
 # which a block runs as tap GEMM at the low resolution + tap-sum resize instead of resize + 3 x 3 convolution.  The
 # per-layer times at 1 and 8 objects (tools/time_psp_conv_before_resize.py) have NOT been taken yet: 4 follows
@@ -95,7 +99,10 @@ def _block_split(blk, xs, x32, need32=True, needs=True):
 class ResNet18(nn.Module):
     """[B,3,H,W] uint8-range float -> [B,512,H/8,W/8] (dense_fusion/resnet.py:9-58)."""
 
-    split_bf16 = True  # res4 / res5 as split-bf16 GEMMs in fp32 inference (module docstring)
+    split_bf16 = True  # res2 .. res5 as split-bf16 GEMMs in fp32 inference (module docstring)
+    # the stem's pool + res2 / res3 on that path (DESIGN.md 8.1); MF_FRONT_SPLIT=0 starts a process with the switch off
+    # (A/B runs of bench.py): torch's max-pool, res2 / res3 on MIOpen, as before
+    front_split = os.environ.get("MF_FRONT_SPLIT", "1") != "0"
 
     mean_rgb = (0.485, 0.456, 0.406)
     std_rgb = (0.229, 0.224, 0.225)
@@ -110,19 +117,31 @@ class ResNet18(nn.Module):
         self.register_buffer("mean", torch.tensor(self.mean_rgb).view(1, 3, 1, 1))
         self.register_buffer("std", torch.tensor(self.std_rgb).view(1, 3, 1, 1))
 
+    @staticmethod
+    def _blocks_split(blocks, xs, x32):
+        """The blocks on split maps, each writing only the forms its reader takes -> fp32 [B,h,w,C] of the last one."""
+        for i, blk in enumerate(blocks):
+            nxt = blocks[i + 1] if i + 1 < len(blocks) else None
+            # fp32 for the next block's identity shortcut and for the output; split form for the next block only
+            xs, x32 = _block_split(blk, xs, x32, need32=nxt is None or nxt.residual_conv is None,
+                                   needs=nxt is not None)
+        return x32
+
     def forward(self, x):
         h = (x / 255.0 - self.mean) / self.std
         h = self.conv1(h)
+        if self.front_split and _split_path(self, h, "res2_res3"):
+            # the stem's pool writes res2.0's operands (fp32 for the identity shortcut, split form for the GEMMs) from
+            # conv1's output where MIOpen left it; res2 / res3 follow as res4 / res5 do
+            x32, xs = ops2d.maxpool_split(h)
+            back = h.shape[0] >= SPLIT_MIN_BATCH["res4_res5"]
+            blocks = list(self.res2) + list(self.res3) + (list(self.res4) + list(self.res5) if back else [])
+            h = self._blocks_split(blocks, xs, x32).permute(0, 3, 1, 2)  # channels-last memory
+            return h if back else self.res5(self.res4(h))
         h = F.max_pool2d(h, 3, 2, 1)
         h = self.res3(self.res2(h))
         if _split_path(self, h, "res4_res5"):
-            blocks = list(self.res4) + list(self.res5)
-            xs, x32 = ops2d.to_split(h), None
-            for i, blk in enumerate(blocks):
-                nxt = blocks[i + 1] if i + 1 < len(blocks) else None
-                # fp32 for the next block's identity shortcut and for the output; split form for the next block only
-                xs, x32 = _block_split(blk, xs, x32, need32=nxt is None or nxt.residual_conv is None,
-                                       needs=nxt is not None)
+            x32 = self._blocks_split(list(self.res4) + list(self.res5), ops2d.to_split(h), None)
             return x32.permute(0, 3, 1, 2)  # [B,512,h,w] in channels-last memory
         return self.res5(self.res4(h))
 
@@ -332,7 +351,6 @@ class PSPNetExtractor(nn.Module):
     # up1 / up2 of the split path: convolution at the low resolution, then the resize; MF_CONV_BEFORE_RESIZE=0
     # starts a process with the switch off (A/B runs of bench.py)
     conv_before_resize = os.environ.get("MF_CONV_BEFORE_RESIZE", "1") != "0"
-
     def _conv_first(self, x, layer):
         return self.conv_before_resize and x.shape[0] >= CONV_BEFORE_RESIZE_MIN_BATCH[layer]
 

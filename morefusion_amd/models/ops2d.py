@@ -217,7 +217,7 @@ def split_pack(conv):
     wf = w.detach().float().contiguous()
     _lib.check(_lib.lib().mf_conv2d_split_pack(wf.data_ptr(), Cout, Cin, k, wp.data_ptr(), _lib.stream_ptr()),
                "mf_conv2d_split_pack")
-    if not torch.cuda.is_current_stream_capturing():
+    if not (w.is_cuda and torch.cuda.is_current_stream_capturing()):
         conv.__dict__["_split_pack"] = (key, wp)
     return wp
 
@@ -329,4 +329,19 @@ def upsample_tapsum(z, bias, act=0, slope=None, out32=True, outs=False):
     _lib.check(_lib.lib().mf_upsample2x_tapsum_fwd(z.data_ptr(), bias.data_ptr(), _lib.ptr(slope), act, _lib.ptr(y32), C,
                                                    _lib.ptr(ys), 2 * C, C, B, H, W, C, _lib.stream_ptr()),
                "mf_upsample2x_tapsum_fwd")
+    return y32, ys
+
+
+# ---- the 2-D front end of fp32 inference -----------------------------------------------------------
+
+def maxpool_split(x, out32=True, outs=True):
+    """``F.max_pool2d(x, 3, 2, 1)`` of fp32 x [B, C, H, W] (any strides, read in place) -> (fp32 channels-last
+    [B, Ho, Wo, C] or None, its split form [B, Ho, Wo, 2C] or None), one launch."""
+    _lib.require_gpu(x)
+    B, C, H, W = x.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y32 = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=x.device) if out32 else None
+    ys = torch.empty((B, Ho, Wo, 2 * C), dtype=torch.bfloat16, device=x.device) if outs else None
+    _lib.check(_lib.lib().mf_maxpool3s2_split_fwd(x.data_ptr(), *x.stride(), B, C, H, W, _lib.ptr(y32), _lib.ptr(ys),
+                                                  _lib.stream_ptr()), "mf_maxpool3s2_split_fwd")
     return y32, ys

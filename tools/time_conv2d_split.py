@@ -1,6 +1,10 @@
 """Per-layer time of the 2-D backbone's in-scope convolutions: MIOpen fp32 (the layer as the stock path runs it) vs the
 split-bf16 GEMM (ops2d.conv_split, epilogue included), 1 and 8 objects, and Model.predict with the split path on / off.
-CUDA-event medians over --reps launches after a warm-up.  -> one JSON line per measurement."""
+CUDA-event medians over --reps launches after a warm-up.  -> one JSON line per measurement.
+
+--front: the front end instead -- res2 / res3's layers alone (MIOpen on the NCHW map it gets, the split GEMM with its
+epilogue), the stem pool and the layer GROUP with its glue (pool + res2 + res3 as the stock modules run them against
+maxpool_split + the split blocks), at --batches objects -> --csv (profiles/frontend_split_layers.csv)."""
 import argparse
 import json
 import statistics
@@ -42,13 +46,61 @@ def timed(fn, reps):
     return statistics.median(ts)
 
 
+FRONT_LAYERS = {  # name: (Cin, Cout, ks, stride, input side, act, calls per predict)
+    "res2.conv 3x3 64->64": (64, 64, 3, 1, 64, 1, 4),
+    "res3.0.conv1 3x3 s2 64->128": (64, 128, 3, 2, 64, 1, 1),
+    "res3 3x3 128->128": (128, 128, 3, 1, 32, 1, 3),
+    "res3.residual 1x1 s2 64->128": (64, 128, 1, 2, 64, 0, 1),
+}
+
+
+def front(args):
+    rows = []
+
+    def emit(**kw):
+        rows.append(kw)
+        print(json.dumps(kw), flush=True)
+
+    with torch.no_grad():
+        res = backbone2d.ResNet18().cuda().eval()
+        for B in [int(b) for b in args.batches.split(",")]:
+            for name, (Cin, Cout, ks, stride, D, act, calls) in FRONT_LAYERS.items():
+                conv = nn.Conv2d(Cin, Cout, ks, stride, padding=ks // 2, bias=False).cuda().eval()
+                x = torch.randn(B, Cin, D, D, device="cuda")
+                xs = ops2d.to_split(x)
+                emit(B=B, what=name, calls=calls, stock_ms=round(timed(lambda: conv(x), args.reps), 4),
+                     new_ms=round(timed(lambda: ops2d.conv_split(xs, conv, act=act, out32=False, outs=True), args.reps), 4))
+            c1 = torch.randn(B, 64, 128, 128, device="cuda")  # conv1's output, NCHW as MIOpen leaves it
+
+            def stock_front():
+                return res.res3(res.res2(F.max_pool2d(c1, 3, 2, 1)))
+
+            def split_front():
+                x32, xs = ops2d.maxpool_split(c1)
+                return backbone2d.ResNet18._blocks_split(list(res.res2) + list(res.res3), xs, x32)
+
+            emit(B=B, what="stem pool alone", calls=1, stock_ms=round(timed(lambda: F.max_pool2d(c1, 3, 2, 1), args.reps), 4),
+                 new_ms=round(timed(lambda: ops2d.maxpool_split(c1), args.reps), 4))
+            emit(B=B, what="group: pool + res2 + res3 with glue", calls=1, stock_ms=round(timed(stock_front, args.reps), 4),
+                 new_ms=round(timed(split_front, args.reps), 4))
+    if args.csv:
+        with open(args.csv, "w") as f:
+            f.write("objects,what,calls_per_predict,stock_ms,new_ms\n")
+            for r in rows:
+                f.write(f"{r['B']},{r['what']},{r['calls']},{r['stock_ms']},{r['new_ms']}\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--front", action="store_true", help="the front end (stem pool, res2 / res3) instead")
+    ap.add_argument("--csv", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-predict", action="store_true")
     ap.add_argument("--batches", default="1,8")
     args = ap.parse_args()
     torch.backends.cudnn.benchmark = False
+    if args.front:
+        return front(args)
     slope = torch.tensor([0.25], device="cuda")
     with torch.no_grad():
         for B in [int(b) for b in args.batches.split(",")]:
