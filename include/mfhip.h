@@ -1121,6 +1121,66 @@ int mf_augment_rgb(const uint8_t *rgb, const double *params, int32_t n, int32_t 
 int mf_augment_pcd(const void *pcd, int32_t pcd_is_f64, const double *params, int32_t n, int32_t S,
                    int64_t seed, void *pcd_out, mfStream_t stream);
 
+/* ---- OccupancyRegistration for a batch of objects (contrib/occupancy_registration.py, csrc/occreg.hip) -------
+ * morefusion/contrib/occupancy_registration.py for B objects in one launch: one workgroup per object runs every
+ * iteration {soft occupancy grid of the transformed points, penalty - reward, backward, chainer-Adam step} with no
+ * host involvement (DESIGN.md "Occupancy registration"; tests/occreg_ref.py is the NumPy mirror, bit for bit).
+ * Object b: points rows pts_off[b] .. pts_off[b + 1] of `points` (float32 [Ptot, 3]); grid dims[b] = (X, Y, Z) of
+ * pitch[b] at origin[b]; threshold[b] in voxels; its targets grid_occ / grid_unocc are the X Y Z floats at
+ * grid_off[b] (grid_off[b + 1] - grid_off[b] = X Y Z; unocc = max(grid[1], grid[2]) for 3-channel targets);
+ * active [B] uint8 (NULL: all): an inactive object's pose passes through, its losses are 0.
+ * All of these are DEVICE arrays.  A launcher cannot read them without synchronising, so the small per-object arrays
+ * travel a second time as HOST arrays (host_*, the same values): the refusals below are decided on those, and the
+ * kernel checks the device copies again (an object whose device descriptor is invalid passes through with a NaN
+ * loss and touches nothing).
+ * Limits: 1 .. MF_OCCREG_MAX_OBJECTS objects; n_points_total and every object's X Y Z (<= max_voxels) and the
+ * batch's voxel total within int32; every dimension >= 1; 0 < threshold <= MF_OCCREG_MAX_THRESHOLD (finite);
+ * pitch finite and > 0: anything else returns -hipErrorInvalidValue with mf_last_error_string set.  Points must be
+ * finite.  A grid of at most MF_OCCREG_LDS_VOXELS voxels keeps its distance field in LDS, a larger one in the
+ * workspace; the first MF_OCCREG_POINT_TILE points of an object keep their grid coordinates in LDS, later ones
+ * are transformed again from global memory.  Every call is asynchronous on `stream`, allocates nothing and never
+ * synchronises; results are bitwise reproducible (no float atomics). */
+#define MF_OCCREG_MAX_OBJECTS 65535
+#define MF_OCCREG_POINT_TILE 1024
+#define MF_OCCREG_LDS_VOXELS 32768
+#define MF_OCCREG_MAX_THRESHOLD 64.0f
+#define MF_OCCREG_STEPS_PER_LAUNCH 128 /* mf_occreg_refine: one launch per this many iterations */
+typedef struct {
+  const float *points;
+  const int32_t *pts_off;
+  const float *pitch;
+  const float *origin;
+  const int32_t *dims;
+  const float *threshold;
+  const float *grid_occ;
+  const float *grid_unocc;
+  const int32_t *grid_off;
+  const uint8_t *active;
+  const int32_t *host_pts_off;
+  const float *host_pitch;
+  const int32_t *host_dims;
+  const float *host_threshold;
+  int32_t n_objects;
+  int32_t n_points_total;
+  int32_t max_voxels;
+  int32_t reserved;
+} mfOccRegBatch;
+/* Host-only: bytes of `workspace` (0 when max_voxels <= MF_OCCREG_LDS_VOXELS: it may then be NULL); < 0 for
+ * n_objects outside 1 .. MF_OCCREG_MAX_OBJECTS, n_points_total < 0, max_voxels < 1 or either beyond int32. */
+int64_t mf_occreg_workspace_bytes(int64_t n_objects, int64_t n_points_total, int64_t max_voxels);
+/* One forward and backward at the poses q [B, 4] (wxyz), t [B, 3] (untouched): loss [B] = sum(unocc m) / sum(m) -
+ * sum(occ m) / sum(occ) (NaN when no voxel is within threshold of a point, as in the reference; the gradient is
+ * then 0), gq [B, 4], gt [B, 3]. */
+int mf_occreg_loss_grad(const mfOccRegBatch *batch, const float *q, const float *t, float *loss, float *gq,
+                        float *gt, void *workspace, mfStream_t stream);
+/* n_iter x {loss, gradient, chainer-Adam step} on q, t, adam_m, adam_v [B, 7] in place; step0 = Adam steps already
+ * taken (bias correction: alpha * sqrt(1 - b2^s) / (1 - b1^s) in double on the host, cast once).  losses
+ * [n_iter, B] (NULL: not kept): losses[k] at the pose before step k + 1; traj [n_iter + 1, B, 7] (NULL: not kept):
+ * entry 0 the initial pose, entry k the pose (q then t) after step k. */
+int mf_occreg_refine(const mfOccRegBatch *batch, float *q, float *t, float *adam_m, float *adam_v, int32_t n_iter,
+                     int32_t step0, float alpha_q, float alpha_t, float *losses, float *traj, void *workspace,
+                     mfStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,15 @@ class RenderBatch(ctypes.Structure):
         (n, _i) for n in ("n_meshes", "n_items", "n_targets", "height", "width", "reserved")]
 
 
+class OccRegBatch(ctypes.Structure):
+    """mfOccRegBatch (include/mfhip.h)."""
+
+    _fields_ = [(n, _p) for n in (
+        "points", "pts_off", "pitch", "origin", "dims", "threshold", "grid_occ", "grid_unocc", "grid_off", "active",
+        "host_pts_off", "host_pitch", "host_dims", "host_threshold")] + [
+        (n, _i) for n in ("n_objects", "n_points_total", "max_voxels", "reserved")]
+
+
 _SIGNATURES = {
     "mf_version": ([], _i),
     "mf_last_error_string": ([], ctypes.c_char_p),
@@ -235,6 +244,9 @@ _SIGNATURES = {
     "mf_pcdnet_stem": ([_p] * 8 + [_i] * 3 + [_p, _p, _i, _p, _i, _i, _p], _i),
     "mf_pcdnet_pool": ([_p, _i64, _i, _i, _i, _p, _p], _i),
     "mf_pcdnet_bias_relu_split": ([_p, _i64, _p, _i, _i, _i, _i, _p, _i64, _p], _i),
+    "mf_occreg_workspace_bytes": ([_i64, _i64, _i64], _i64),
+    "mf_occreg_loss_grad": ([_p] * 8, _i),  # (mfOccRegBatch by reference: ctypes.byref(OccRegBatch))
+    "mf_occreg_refine": ([_p] * 5 + [_i, _i, _f, _f] + [_p] * 4, _i),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -3,7 +3,7 @@
 from .icc_batch import IccScenes
 from .iterative_closest_point_link import IterativeClosestPointLink, icp_refine
 from .iterative_collision_check_link import IterativeCollisionCheckLink
-from .occupancy_registration import OccupancyRegistration, OccupancyRegistrationLink
+from .occupancy_registration import OccupancyRegistration, OccupancyRegistrationLink, occupancy_registration_batch
 from . import singleview_3d
 from . import singleview_pcd
 from .multi_instance_octree_mapping import MultiInstanceOctreeMapping

@@ -10,6 +10,11 @@ metric vectors are the only copies to the host.
 Where this differs from the reference: ICC starts from the network's quaternion and translation themselves (the
 reference goes through the 4 x 4 matrix and back, ``quaternion_from_matrix``), and all objects are refined in one
 batched launch per stage.  ICP results are cast to float32, as the reference's ``np.array(..., dtype=np.float32)``.
+
+The opt-in method ``"occupancy"`` (not in ``METHODS``) refines the arg-max poses with ``occupancy_registration_batch``
+-- the reference's examples/ycb_video/dense_fusion/eval_densefusion_occupancy.py:94-114 with this network's poses
+as the start: the CAD cloud voxel-down-sampled at the object's pitch against ``grid_target`` (occupied) and
+``grid_nontarget_empty`` (unoccupied), threshold 2, alpha 0.01; a registration that ends in NaN keeps the start.
 """
 import numpy as np
 import torch
@@ -19,8 +24,11 @@ from ...functions.geometry.transformation_matrix import transformation_matrix_ba
 from ...synthetic import CLASS_IDS_SYMMETRIC
 from ..icc_batch import IccScenes
 from ..icp_registration import icp_registration_batch
+from ..occupancy_registration import occupancy_registration_batch
 
 METHODS = ("morefusion", "morefusion+icp", "morefusion+icc", "morefusion+icc+icp")
+OPTIONAL_METHODS = ("occupancy",)  # accepted by evaluate_batch, not run by default
+OCCUPANCY_THRESHOLD, OCCUPANCY_ALPHA = 2, 0.01  # eval_densefusion_occupancy.py:103-108
 ICC_ALPHA_QUATERNION, ICC_ALPHA_TRANSLATION = 0.01, 0.001  # evaluate.py:261-263
 
 
@@ -44,7 +52,8 @@ def icc_scene(batch, models, class_ids):
                 grid_target=batch["grid_target"], grid_nontarget_empty=batch["grid_nontarget_empty"])
 
 
-def evaluate_batch(model, batch, models, methods=METHODS, frame_index=0, n_icc=30, n_icp=100, n_icc_icp=30):
+def evaluate_batch(model, batch, models, methods=METHODS, frame_index=0, n_icc=30, n_icp=100, n_icc_icp=30,
+                   n_occ=100):
     """``batch``: the network's inputs for the B objects of one frame, arrays or tensors ``[B, ...]`` -- class_id,
     rgb, pcd, pitch, origin, grid_target, grid_nontarget_empty, quaternion_true, translation_true (the keys of
     ``synthetic.transform_example``, concatenated).  ``models``: ``get_pcd(class_id)`` and ``get_sdf(class_id)``.
@@ -53,8 +62,8 @@ def evaluate_batch(model, batch, models, methods=METHODS, frame_index=0, n_icc=3
     add_or_add_s, add_s, method, the objects of one method after the other -- and ``transforms``: {method: [B,4,4]
     float32 device tensor, cad -> camera}, plus ``"true"``."""
     methods = tuple(methods)
-    if not methods or any(m not in METHODS for m in methods):
-        raise ValueError(f"methods {methods}: one or more of {METHODS}")
+    if not methods or any(m not in METHODS + OPTIONAL_METHODS for m in methods):
+        raise ValueError(f"methods {methods}: one or more of {METHODS + OPTIONAL_METHODS}")
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("evaluate_batch runs on the MI355X: move the model to 'cuda' (there is no CPU fallback)")
@@ -89,6 +98,17 @@ def evaluate_batch(model, batch, models, methods=METHODS, frame_index=0, n_icc=3
                 transforms["morefusion+icc"] = icc
             if "morefusion+icc+icp" in methods:
                 transforms["morefusion+icc+icp"] = icp(icc, n_icc_icp)
+        if "occupancy" in methods:
+            from ...extra import open3d as extra_open3d
+            pitches = [float(p) for p in torch.as_tensor(batch["pitch"]).reshape(-1).tolist()]
+            sources = [extra_open3d.voxel_down_sample(
+                torch.as_tensor(np.asarray(models.get_pcd(c), np.float64)).to(dev), p).float()
+                for c, p in zip(class_ids, pitches)]
+            grids = torch.stack([b["grid_target"].float(), b["grid_nontarget_empty"].float()], dim=1)
+            transforms["occupancy"] = occupancy_registration_batch(
+                sources, grids, pitch=b["pitch"].float().reshape(-1), origin=b["origin"].float().reshape(B, 3),
+                threshold=OCCUPANCY_THRESHOLD, transforms_init=transforms["morefusion"], iteration=n_occ,
+                alpha=OCCUPANCY_ALPHA, device=dev, pose_init=(quaternion, translation))[0]
         # every (method, object) item in one launch: the distinct classes' clouds, ground truth as transform1
         classes = sorted(set(class_ids))
         clouds = [models.get_pcd(c) for c in classes]
