@@ -9,6 +9,9 @@ synthetic primitives; their SDF values are synthetic (the YCB SDFs are a downloa
 solid points and signed distances, computed on the device).
   --mode step   : the reference's loop (loss.backward(); optimizer.update(); zerograds())
   --mode fused  : link.refine() -- the whole loop as one hipGraph on the device
+  --until-converged : the loop of the reference's ROS node (collision_based_pose_refinement.py:178-207: at most 30
+                  iterations, left once its LossObserver validates), decided on the device per scene
+                  (link.refine_until_converged()), next to the fixed 30-iteration loop from the same start
 """
 import argparse
 import os
@@ -29,6 +32,8 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--cad-dir", help="YCB-Video model directory (<NNN_name>/textured*.obj): the fixture objects' "
                     "points and SDF from the CAD meshes instead of the synthetic stand-in")
+    ap.add_argument("--until-converged", action="store_true",
+                    help="the ROS node's loop (<= 30 iterations, stops once the loss has converged) beside the fixed 30")
     args = ap.parse_args()
 
     gold = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
@@ -48,6 +53,24 @@ def main():
     pitch, origin = to_gpu(data["pitch"]), to_gpu(data["origin"])
     grid_target = to_gpu(data["grid_target"])
     grid_nontarget_empty = to_gpu(data["grid_nontarget_empty"])
+
+    if args.until_converged:
+        inputs = (points, sdf, pitch, origin, grid_target, grid_nontarget_empty)
+        fixed = morefusion.contrib.IterativeCollisionCheckLink(data["transform_init"], sdf_offset=0.02).to_gpu()
+        losses_f, _ = fixed.refine(*inputs, n_iter=30, return_history=True)
+        link = morefusion.contrib.IterativeCollisionCheckLink(data["transform_init"], sdf_offset=0.02).to_gpu()
+        n_steps, losses_c, _ = link.refine_until_converged(*inputs, sync=True, return_history=True)
+        n = int(n_steps[0])
+        T_f = morefusion.functions.transformation_matrix(fixed.quaternion, fixed.translation).detach()
+        T_c = morefusion.functions.transformation_matrix(link.quaternion, link.translation).detach()
+        print(f"scene 0: {n} steps until converged (of at most 30); last loss {float(losses_c[n - 1]):.5f}, "
+              f"fixed 30 iterations: {float(losses_f[-1]):.5f}")
+        # ADD of the converged pose against the fixed loop's, per object: mean distance of the model points
+        for k, p in enumerate(points):
+            a = p @ T_c[k, :3, :3].T + T_c[k, :3, 3]
+            b = p @ T_f[k, :3, :3].T + T_f[k, :3, 3]
+            print(f"  object {k}: ADD against the fixed 30-iteration pose {float((a - b).norm(dim=1).mean()) * 1e3:.3f} mm")
+        return
 
     link = morefusion.contrib.IterativeCollisionCheckLink(data["transform_init"], sdf_offset=0.02)
     link.to_gpu()

@@ -224,6 +224,33 @@ int mf_icc_refine(const mfIccBatch *batch, float *q, float *t, float *adam_m,
                   float alpha_t, float *losses, float *traj, void *ws,
                   mfStream_t stream);
 
+/* Bytes of the caller-provided loss-observer buffer of mf_icc_refine_converge: two copies of one record per scene
+ * (negative: n_scenes <= 0, or window outside 1 .. 16).  8-byte aligned; its contents need no initialisation. */
+int64_t mf_icc_observer_bytes(int32_t n_scenes, int32_t window);
+
+/* mf_icc_refine until each scene's loss has converged, decided on the device: at most max_iter iterations in one
+ * hipGraph launch, no host sync, same conventions as mf_icc_refine.  Every scene carries the LossObserver of the
+ * reference's ROS node (ros/src/morefusion_ros/nodes/collision_based_pose_refinement.py:18-45; its constants:
+ * max_delta_threshold 0.009, window 10, n_passed_threshold 3, max_iter 30), fed after the optimiser step of
+ * iteration i (0-based; that step IS applied) with loss_i = losses[i, s]:
+ *   i >= 1: delta = |double(loss_{i-1}) - double(loss_i)| enters a window of the `window` most recent deltas;
+ *   window not empty: every delta in it < max_delta_threshold (in double) -> n_passed += 1, otherwise n_passed = 0;
+ *   n_passed >= n_passed_threshold -> the scene is converged and FROZEN: from the next iteration on none of its
+ *   objects takes a step, while the other scenes of the batch go on.
+ * Departure from the node, on purpose: while the window holds a non-finite delta the step does not pass (n_passed
+ * = 0).  Python's max() over a list holding a NaN depends on the order of the list; this rule does not.
+ * Outputs: n_steps [S] = steps applied to each scene (max_iter if it never converged); q, t, adam_m, adam_v of
+ * every object = bit for bit what mf_icc_refine with n_iter = n_steps[s] leaves for its scene; rows < n_steps[s] of
+ * losses [max_iter,S] / traj [max_iter,O,7] (either may be NULL) as mf_icc_refine writes them, rows >= n_steps[s]
+ * of that scene's columns NOT written (pre-fill them).  step0 as in mf_icc_refine; every call starts with fresh
+ * observers.  observer: mf_icc_observer_bytes(n_scenes, window) bytes.  Negative return, nothing launched: max_iter
+ * < 1, window outside 1 .. 16, observer or n_steps NULL. */
+int mf_icc_refine_converge(const mfIccBatch *batch, float *q, float *t, float *adam_m, float *adam_v,
+                           int32_t max_iter, int32_t step0, float alpha_q, float alpha_t,
+                           double max_delta_threshold, int32_t window, int32_t n_passed_threshold,
+                           float *losses, float *traj, int32_t *n_steps, void *observer,
+                           void *ws, mfStream_t stream);
+
 /* Launches per iteration mf_icc_refine will use for this batch: 2 = k_icc_bin + k_icc_fused ({0,1} no-entry grids:
  * the default), 3 = k_icc_bin + k_icc_tile + k_icc_accum (any no-entry grid values).  Negative: invalid descriptor. */
 int mf_icc_iteration_launches(const mfIccBatch *batch);

@@ -104,6 +104,9 @@ _SIGNATURES = {
     "mf_icc_prepare": ([ctypes.POINTER(IccBatch), _p, _p], _i),
     "mf_icc_loss_grad": ([ctypes.POINTER(IccBatch), _p, _p, _p, _p, _p, _p, _p], _i),
     "mf_icc_refine": ([ctypes.POINTER(IccBatch), _p, _p, _p, _p, _i, _i, _f, _f, _p, _p, _p, _p], _i),
+    "mf_icc_observer_bytes": ([_i, _i], _i64),
+    "mf_icc_refine_converge": ([ctypes.POINTER(IccBatch), _p, _p, _p, _p, _i, _i, _f, _f, _d, _i, _i, _p, _p, _p, _p, _p,
+                                _p], _i),
     "mf_icc_debug_stamps": ([_p, _i], _i),
     "mf_sparse_conv3d_workspace_bytes": ([_i] * 5 + [_i64], _i64),
     "mf_sparse_conv3d_k4s2_points_fwd": ([_p, _p, _p, _i64, _f, _f, _f, _f, _p, _p, _p, _p, _p] + [_i] * 6 + [_p], _i),

@@ -3,6 +3,7 @@
 from .icc_batch import IccScenes
 from .iterative_closest_point_link import IterativeClosestPointLink, icp_refine
 from .iterative_collision_check_link import IterativeCollisionCheckLink
+from .loss_observer import LossObserver
 from .occupancy_registration import OccupancyRegistration, OccupancyRegistrationLink, occupancy_registration_batch
 from . import singleview_3d
 from . import singleview_pcd

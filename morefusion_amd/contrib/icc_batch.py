@@ -4,7 +4,7 @@ Packs the reference's argument lists
 (``link(points, sdf, pitch, origin, grid_target, grid_nontarget_empty)``,
 morefusion/contrib/iterative_collision_check_link.py:31-33) for one or many independent
 scenes into the flat device arrays ``mfIccBatch`` describes (include/mfhip.h) and
-owns the workspace of ``mf_icc_loss_grad`` / ``mf_icc_refine``.
+owns the workspace of ``mf_icc_loss_grad`` / ``mf_icc_refine`` / ``mf_icc_refine_converge``.
 """
 import ctypes
 import os
@@ -87,6 +87,7 @@ class IccScenes:
             raise ValueError("mf_icc: invalid batch descriptor (objects per scene <= 128 with {0,1} no-entry grids, <= 64 "
                              "with other values; dim <= 64)")
         self.ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        self._observer = None  # loss-observer records of refine_until_converged, allocated on first use
         self.prepare()
 
     def prepare(self):
@@ -130,3 +131,37 @@ class IccScenes:
                                      float(alpha_q), float(alpha_t), _lib.ptr(losses),
                                      _lib.ptr(traj), self.ws.data_ptr(), _lib.stream_ptr()),
             "mf_icc_refine")
+
+    def refine_until_converged(self, q, t, adam_m, adam_v, max_iter=30, step0=0, alpha_q=0.01, alpha_t=0.001,
+                               max_delta_threshold=0.009, window=10, n_passed_threshold=3, losses=None, traj=None):
+        """``refine`` until each scene's loss has converged, decided on the device: the loop of the reference's ROS
+        node (collision_based_pose_refinement.py:184-207: at most 30 iterations, a ``LossObserver`` fed after every
+        optimiser step) with one observer per scene, in one hipGraph launch without host synchronisation.  A
+        converged scene is frozen -- its objects take no further step -- while the others go on.
+
+        Returns ``n_steps`` [S] int32 on the device: the steps applied to each scene (``max_iter`` if it never
+        converged).  In place, ``q, t, adam_m, adam_v`` of every object end up bit for bit where
+        ``refine(n_iter=n_steps[s])`` leaves them.  ``losses`` [max_iter,S] / ``traj`` [max_iter,O,7]: rows
+        ``< n_steps[s]`` as ``refine`` writes them, the rows from ``n_steps[s]`` on of that scene's columns are
+        NOT written -- pre-fill them.  Rule and constants: ``contrib.LossObserver``, including its one departure
+        from the node: a non-finite delta in the window fails the step (the node's ``max`` over a list holding a
+        NaN depends on the list's order)."""
+        for x in (q, t, adam_m, adam_v):
+            _lib.require_gpu(x)
+            if x.dtype != torch.float32 or not x.is_contiguous():
+                raise TypeError("refine_until_converged() needs contiguous float32 state tensors")
+        L = _lib.lib()
+        nbytes = L.mf_icc_observer_bytes(self.n_scenes, int(window))
+        if nbytes < 0 or int(max_iter) < 1:
+            raise ValueError("refine_until_converged: window must be 1 .. 16 and max_iter >= 1")
+        if self._observer is None or self._observer.numel() < nbytes:
+            self._observer = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        n_steps = torch.empty((self.n_scenes,), dtype=torch.int32, device=self.device)
+        _lib.check(
+            L.mf_icc_refine_converge(ctypes.byref(self.desc), q.data_ptr(), t.data_ptr(), adam_m.data_ptr(),
+                                     adam_v.data_ptr(), int(max_iter), int(step0), float(alpha_q), float(alpha_t),
+                                     float(max_delta_threshold), int(window), int(n_passed_threshold),
+                                     _lib.ptr(losses), _lib.ptr(traj), n_steps.data_ptr(),
+                                     self._observer.data_ptr(), self.ws.data_ptr(), _lib.stream_ptr()),
+            "mf_icc_refine_converge")
+        return n_steps

@@ -113,3 +113,51 @@ class IterativeCollisionCheckLink(torch.nn.Module):
         self.translation.data.copy_(t)
         if return_history:
             return losses[:, 0], traj
+
+    @torch.no_grad()
+    def refine_until_converged(self, points, sdf, pitch, origin, grid_target, grid_nontarget_empty, max_iter=30,
+                               alpha=0.01, translation_alpha_scale=0.1, max_delta_threshold=0.009, window=10,
+                               n_passed_threshold=3, sync=False, return_history=False):
+        """The loop of the reference's ROS node (collision_based_pose_refinement.py:178-207: Adam(0.01),
+        translation alpha x0.1, at most 30 iterations, left once its ``LossObserver`` validates) on the device,
+        without a host round trip per iteration.  Updates the parameters in place and returns ``n_steps`` ([1]
+        int32 on the device): the optimiser steps taken.
+
+        The link's Adam step counter has to advance by that number, which only the device knows: ``sync=True``
+        reads it back (one host synchronisation) and the link may be refined further; with ``sync=False`` nothing
+        waits, and the link must NOT be refined again (``refine_until_converged`` raises; ``refine`` is not guarded) until
+        ``sync_adam_counter()`` has been called.  ``return_history``: also (losses [max_iter], trajectory
+        [max_iter,N,7]), NaN from row ``n_steps`` on."""
+        if getattr(self, "_adam_pending", None) is not None:
+            raise RuntimeError("the Adam step counter of this link is still on the device: call sync_adam_counter()")
+        scenes = self._pack(points, sdf, pitch, origin, grid_target, grid_nontarget_empty)
+        dev = self.quaternion.device
+        N = self.quaternion.shape[0]
+        if getattr(self, "_adam", None) is None:
+            self._adam = [torch.zeros((N, 7), dtype=torch.float32, device=dev) for _ in range(2)]
+            self._adam_t = 0
+        q = self.quaternion.data.contiguous()
+        t = self.translation.data.contiguous()
+        losses = traj = None
+        if return_history:
+            losses = torch.full((max_iter, 1), float("nan"), dtype=torch.float32, device=dev)
+            traj = torch.full((max_iter, N, 7), float("nan"), dtype=torch.float32, device=dev)
+        n_steps = scenes.refine_until_converged(
+            q, t, self._adam[0], self._adam[1], max_iter=max_iter, step0=self._adam_t, alpha_q=alpha,
+            alpha_t=alpha * translation_alpha_scale, max_delta_threshold=max_delta_threshold, window=window,
+            n_passed_threshold=n_passed_threshold, losses=losses, traj=traj)
+        self.quaternion.data.copy_(q)
+        self.translation.data.copy_(t)
+        self._adam_pending = n_steps
+        if sync:
+            self.sync_adam_counter()
+        if return_history:
+            return n_steps, losses[:, 0], traj
+        return n_steps
+
+    def sync_adam_counter(self):
+        """Advance the Adam step counter by the steps the last ``refine_until_converged`` took (one host sync)."""
+        pending = getattr(self, "_adam_pending", None)
+        if pending is not None:
+            self._adam_t += int(pending.max().item())
+            self._adam_pending = None

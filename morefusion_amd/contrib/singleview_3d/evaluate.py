@@ -53,14 +53,19 @@ def icc_scene(batch, models, class_ids):
 
 
 def evaluate_batch(model, batch, models, methods=METHODS, frame_index=0, n_icc=30, n_icp=100, n_icc_icp=30,
-                   n_occ=100):
+                   n_occ=100, icc_until_converged=False):
     """``batch``: the network's inputs for the B objects of one frame, arrays or tensors ``[B, ...]`` -- class_id,
     rgb, pcd, pitch, origin, grid_target, grid_nontarget_empty, quaternion_true, translation_true (the keys of
     ``synthetic.transform_example``, concatenated).  ``models``: ``get_pcd(class_id)`` and ``get_sdf(class_id)``.
 
     Returns ``(rows, transforms)``: the reference's rows -- dicts with frame_index, batch_index, class_id,
     add_or_add_s, add_s, method, the objects of one method after the other -- and ``transforms``: {method: [B,4,4]
-    float32 device tensor, cad -> camera}, plus ``"true"``."""
+    float32 device tensor, cad -> camera}, plus ``"true"``.
+
+    ``icc_until_converged`` (default off: nothing changes): the ICC methods run the loop of the reference's ROS node
+    -- at most ``n_icc`` iterations, left once the loss has converged (``IccScenes.refine_until_converged``, the
+    node's constants) -- and the result carries the steps taken: ``transforms["icc_n_steps"]`` ([1] int32 device
+    tensor; no host synchronisation is added)."""
     methods = tuple(methods)
     if not methods or any(m not in METHODS + OPTIONAL_METHODS for m in methods):
         raise ValueError(f"methods {methods}: one or more of {METHODS + OPTIONAL_METHODS}")
@@ -92,7 +97,11 @@ def evaluate_batch(model, batch, models, methods=METHODS, frame_index=0, n_icc=3
             q, t = quaternion.clone(), translation.clone()
             adam_m = torch.zeros((B, 7), dtype=torch.float32, device=dev)
             adam_v = torch.zeros((B, 7), dtype=torch.float32, device=dev)
-            scenes.refine(q, t, adam_m, adam_v, n_icc, alpha_q=ICC_ALPHA_QUATERNION, alpha_t=ICC_ALPHA_TRANSLATION)
+            if icc_until_converged:
+                icc_n_steps = scenes.refine_until_converged(q, t, adam_m, adam_v, max_iter=n_icc,
+                                                            alpha_q=ICC_ALPHA_QUATERNION, alpha_t=ICC_ALPHA_TRANSLATION)
+            else:
+                scenes.refine(q, t, adam_m, adam_v, n_icc, alpha_q=ICC_ALPHA_QUATERNION, alpha_t=ICC_ALPHA_TRANSLATION)
             icc = transformation_matrix_batch(q, t)
             if "morefusion+icc" in methods:
                 transforms["morefusion+icc"] = icc
@@ -123,4 +132,7 @@ def evaluate_batch(model, batch, models, methods=METHODS, frame_index=0, n_icc=3
             add, add_s = float(adds[k * B + i]), float(add_ss[k * B + i])
             rows.append(dict(frame_index=frame_index, batch_index=i, class_id=cid,
                              add_or_add_s=add_s if cid in CLASS_IDS_SYMMETRIC else add, add_s=add_s, method=method))
-    return rows, {m: transforms[m] for m in ("true",) + methods}
+    out = {m: transforms[m] for m in ("true",) + methods}
+    if icc_until_converged and any("icc" in m for m in methods):
+        out["icc_n_steps"] = icc_n_steps
+    return rows, out

@@ -233,8 +233,15 @@ constexpr int kBigLds = 124 * 1024;  // dynamic LDS every entry point allows the
 #define ICC_LAUNCH(kernel_, l_, stream_, ...) \
   hipLaunchKernelGGL(kernel_, dim3((l_).gx, (l_).gy), dim3((l_).threads), (size_t)(l_).lds, stream_, __VA_ARGS__)
 
-void launch_bin(const IccPlan &p, const IccArgs &a, const IccStepArgs &sp, hipStream_t stream) {
-  ICC_LAUNCH(k_icc_bin, p.bin, stream, a, sp);
+// (ob: the loss observer of mf_icc_refine_converge, which rides on the steps; NULL everywhere else)
+void launch_bin(const IccPlan &p, const IccArgs &a, const IccStepArgs &sp, hipStream_t stream,
+                const IccObsArgs *ob = nullptr) {
+  if (ob && sp.mode == 1) {
+    const IccObsArgs o = *ob;  // (a copy of this launch's own)
+    ICC_LAUNCH(k_icc_bin<true>, p.bin, stream, a, sp, o);
+  } else {
+    ICC_LAUNCH(k_icc_bin<false>, p.bin, stream, a, sp, IccNoObs{});
+  }
 }
 void launch_tile(const IccPlan &p, const IccArgs &a, int par, hipStream_t stream) {
   ICC_LAUNCH(k_icc_tile, p.tile, stream, a, par);
@@ -247,17 +254,24 @@ void launch_fused(const IccPlan &p, const IccArgs &a, int par, hipStream_t strea
   if (MF_ICC_DEBUG_BUILD && p.fused.lds > kBigLds) mf::allow_big_lds((const void *)kernel, p.fused.lds);  // (MF_ICC_LDS_PAD)
   ICC_LAUNCH(kernel, p.fused, stream, a, par);
 }
-void launch_step(const IccPlan &p, const IccArgs &a, const IccStepArgs &sp, hipStream_t stream) {
-  ICC_LAUNCH(k_icc_step, p.step, stream, a, sp);
+void launch_step(const IccPlan &p, const IccArgs &a, const IccStepArgs &sp, hipStream_t stream,
+                 const IccObsArgs *ob = nullptr) {
+  if (ob) {
+    const IccObsArgs o = *ob;
+    ICC_LAUNCH(k_icc_step<true>, p.step, stream, a, sp, o);
+  } else {
+    ICC_LAUNCH(k_icc_step<false>, p.step, stream, a, sp, IccNoObs{});
+  }
 }
 
 // One iteration k (counters / accumulators / maxima of parity k & 1): bin (+ the previous
 // iteration's step when sp.mode == 1), then either the single-pass kernel or tile -> accum.
-void launch_iteration(const IccPlan &p, const IccArgs &a, IccStepArgs sp, int k, hipStream_t stream) {
+void launch_iteration(const IccPlan &p, const IccArgs &a, IccStepArgs sp, int k, hipStream_t stream,
+                      const IccObsArgs *ob = nullptr) {
   const int par = k & 1;
   sp.cpar = par;
   sp.fused = p.single_pass;
-  launch_bin(p, a, sp, stream);
+  launch_bin(p, a, sp, stream, ob);
   if (p.single_pass) {
     launch_fused(p, a, par, stream);
   } else {
@@ -278,6 +292,14 @@ struct GraphKey {
 };
 std::map<GraphKey, hipGraphExec_t> g_graphs;
 std::mutex g_graph_mu;
+
+// the observer of one mf_icc_refine_converge call, as the caller gave it
+struct IccObsCall {
+  void *rec;
+  int32_t *n_steps;
+  double max_delta;
+  int window, n_pass;
+};
 
 }  // namespace
 
@@ -391,14 +413,10 @@ extern "C" int mf_icc_loss_grad(const mfIccBatch *batch, const float *q, const f
   return mf::check_launch("mf_icc_loss_grad");
 }
 
-extern "C" int mf_icc_refine(const mfIccBatch *batch, float *q, float *t, float *adam_m,
-                             float *adam_v, int32_t n_iter, int32_t step0, float alpha_q,
-                             float alpha_t, float *losses, float *traj, void *ws,
-                             mfStream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  IccPlan p;
-  if (int e = icc_enter(batch, p)) return e;
-  if (n_iter <= 0) return 0;
+// The loop of mf_icc_refine (oc == NULL) and of mf_icc_refine_converge: one cached hipGraph, replayed on `stream`.
+static int icc_refine_graph(const mfIccBatch *batch, const IccPlan &p, float *q, float *t, float *adam_m, float *adam_v,
+                            int32_t n_iter, int32_t step0, float alpha_q, float alpha_t, float *losses, float *traj,
+                            const IccObsCall *oc, void *ws, hipStream_t stream) {
   const IccArgs a = make_args(batch, p, ws);
 
   // the key: what the kernels are handed from the caller (pointers, scalars of the descriptor and of this call, the
@@ -419,6 +437,13 @@ extern "C" int mf_icc_refine(const mfIccBatch *batch, float *q, float *t, float 
   int dev = 0;
   MF_TRY(hipGetDevice(&dev));
   key.v.push_back(((uint64_t)(uint32_t)dev << 32) | (uint32_t)a.max_ns);
+  if (oc) {  // (a key of another length than the fixed loop's: the two never meet)
+    push(oc->rec); push(oc->n_steps);
+    uint64_t thr_bits;
+    memcpy(&thr_bits, &oc->max_delta, 8);
+    key.v.push_back(thr_bits);
+    key.v.push_back(((uint64_t)(uint32_t)oc->window << 32) | (uint32_t)oc->n_pass);
+  }
   static_assert(sizeof(IccPlan) % sizeof(uint64_t) == 0, "IccPlan is hashed in 64-bit words");
   key.v.resize(key.v.size() + sizeof(IccPlan) / sizeof(uint64_t));
   memcpy(&key.v[key.v.size() - sizeof(IccPlan) / sizeof(uint64_t)], &p, sizeof(IccPlan));
@@ -439,10 +464,20 @@ extern "C" int mf_icc_refine(const mfIccBatch *batch, float *q, float *t, float 
     float *alt = a.state_alt;
     float *sq[2] = {q, alt}, *st[2] = {t, alt + 4 * a.O}, *sm[2] = {adam_m, alt + 7 * a.O},
           *sv[2] = {adam_v, alt + 14 * a.O};
+    IccObsArgs ob = {};
+    if (oc) {  // fresh observers first: a replay starts where the first launch did
+      ob.rec = (IccObsRec *)oc->rec;
+      ob.n_steps = oc->n_steps;
+      ob.max_delta = oc->max_delta;
+      ob.window = oc->window;
+      ob.n_pass = oc->n_pass;
+      hipLaunchKernelGGL(k_icc_obs_reset, dim3((2 * a.S + 63) / 64), dim3(64), 0, cap, ob.rec, 2 * a.S);
+    }
     hipLaunchKernelGGL(k_icc_pose, dim3(a.O), dim3(256), 0, cap, a, (const float *)q,
                        (const float *)t, traj);
     for (int k = 0; k <= n_iter; ++k) {
       IccStepArgs sp = {};
+      ob.in = (k - 1) & 1;  // step k reads the records step k - 1 wrote (step 1: the fresh ones of copy 0)
       if (k > 0) {
         const int in = (k - 1) & 1, out = k == n_iter ? 0 : (k & 1);
         sp.mode = 1;
@@ -457,10 +492,10 @@ extern "C" int mf_icc_refine(const mfIccBatch *batch, float *q, float *t, float 
       }
       if (k == n_iter) {  // the step of the last iteration, as a kernel of its own
         sp.fused = p.single_pass;
-        launch_step(p, a, sp, cap);
+        launch_step(p, a, sp, cap, oc ? &ob : nullptr);
         break;
       }
-      launch_iteration(p, a, sp, k, cap);
+      launch_iteration(p, a, sp, k, cap, oc ? &ob : nullptr);
     }
     hipError_t ce = hipStreamEndCapture(cap, &graph);
     if (ce != hipSuccess) {
@@ -482,4 +517,38 @@ extern "C" int mf_icc_refine(const mfIccBatch *batch, float *q, float *t, float 
   }
   MF_TRY(hipGraphLaunch(itg->second, stream));
   return 0;
+}
+
+extern "C" int mf_icc_refine(const mfIccBatch *batch, float *q, float *t, float *adam_m,
+                             float *adam_v, int32_t n_iter, int32_t step0, float alpha_q,
+                             float alpha_t, float *losses, float *traj, void *ws,
+                             mfStream_t stream_) {
+  IccPlan p;
+  if (int e = icc_enter(batch, p)) return e;
+  if (n_iter <= 0) return 0;
+  return icc_refine_graph(batch, p, q, t, adam_m, adam_v, n_iter, step0, alpha_q, alpha_t, losses, traj, nullptr, ws,
+                          (hipStream_t)stream_);
+}
+
+extern "C" int64_t mf_icc_observer_bytes(int32_t n_scenes, int32_t window) {
+  if (n_scenes <= 0 || window < 1 || window > kObsMaxWindow) return -1;
+  return (int64_t)2 * n_scenes * (int64_t)sizeof(IccObsRec);
+}
+
+extern "C" int mf_icc_refine_converge(const mfIccBatch *batch, float *q, float *t, float *adam_m, float *adam_v,
+                                      int32_t max_iter, int32_t step0, float alpha_q, float alpha_t,
+                                      double max_delta_threshold, int32_t window, int32_t n_passed_threshold,
+                                      float *losses, float *traj, int32_t *n_steps, void *observer, void *ws,
+                                      mfStream_t stream_) {
+  IccPlan p;
+  if (int e = icc_enter(batch, p)) return e;
+  if (max_iter < 1 || window < 1 || window > kObsMaxWindow || !observer || !n_steps || ((uintptr_t)observer & 7)) {
+    mf::set_last_error(hipErrorInvalidValue,
+                       "mf_icc_refine_converge: needs max_iter >= 1, 1 <= window <= 16, n_steps and an 8-byte aligned "
+                       "observer buffer of mf_icc_observer_bytes()");
+    return -(int)hipErrorInvalidValue;
+  }
+  const IccObsCall oc = {observer, n_steps, max_delta_threshold, window, n_passed_threshold};
+  return icc_refine_graph(batch, p, q, t, adam_m, adam_v, max_iter, step0, alpha_q, alpha_t, losses, traj, &oc, ws,
+                          (hipStream_t)stream_);
 }

@@ -6,8 +6,25 @@
 
 namespace {
 
+// What the designated workgroup of object j empties, all lanes together (one lane storing ~300 words in a row
+// measured 4 us): this object's accumulators and maxima of the parity the coming iteration adds into, and the bins
+// of its two grids that the NEXT iteration fills.
+__device__ __forceinline__ void icc_bin_empties(const IccArgs &a, const IccStepArgs &sp, int j, int nb) {
+  if (threadIdx.x < 2) a.Mbits[(int64_t)(sp.par ^ 1) * 2 * a.O + 2 * j + threadIdx.x] = 0;
+  long long *own = a.acc_own + ((int64_t)(sp.par ^ 1) * a.O + j) * kOwnSlots;
+  for (int i = threadIdx.x; i < kOwnSlots; i += kBinThreads) own[i] = 0;
+  long long *oth = a.acc_oth + ((int64_t)(sp.par ^ 1) * a.O + j) * a.max_ns * 12;
+  for (int i = threadIdx.x; i < a.max_ns * 12; i += kBinThreads) oth[i] = 0;
+  for (int i = threadIdx.x; i < 2 * nb; i += kBinThreads)
+    a.bin_cnt[((int64_t)(sp.cpar ^ 1) * 2 * a.O + 2 * j) * nb + i] = 0u;
+}
+
 // launch 1: one workgroup per (target grid, source object, chunk of <= 1024 points)
-__global__ __launch_bounds__(kBinThreads) void k_icc_bin(IccArgs a, IccStepArgs sp) {
+// OBS (mf_icc_refine_converge): the step carries the scene's loss observer (icc_step.h), and the workgroups of a
+// frozen scene neither step nor bin.  Everything of it sits behind `if constexpr`: k_icc_bin<false> is the kernel
+// the fixed loop always had.
+template <bool OBS>
+__global__ __launch_bounds__(kBinThreads) void k_icc_bin(IccArgs a, IccStepArgs sp, typename IccObsOf<OBS>::type ob) {
   __shared__ int s_cnt[kMaxBins], s_base[kMaxBins];
   __shared__ float s_sum[kStepSums], s_state[kStateFloats];
   __shared__ __attribute__((aligned(16))) float s_Rt12[16];
@@ -44,6 +61,8 @@ __global__ __launch_bounds__(kBinThreads) void k_icc_bin(IccArgs a, IccStepArgs 
     }
     S_t = a.St[e2.z];
   }
+  bool frozen = false;
+  if constexpr (OBS) frozen = sp.mode != 0 && ob.rec[(int64_t)ob.in * a.S + e2.z].frozen != 0;  // block-uniform
   const float4 bnd = *reinterpret_cast<const float4 *>(a.bound + 4 * j);
   const float pitch = a.pitch[o];
   const float ox = a.origin[3 * o], oy = a.origin[3 * o + 1], oz = a.origin[3 * o + 2];
@@ -58,6 +77,28 @@ __global__ __launch_bounds__(kBinThreads) void k_icc_bin(IccArgs a, IccStepArgs 
     m[u] = p < e.w ? a.pts4[p] : make_float4(0, 0, 0, 0);
   }
   for (int i = threadIdx.x; i < nbr; i += kBinThreads) s_cnt[i] = 0;
+  if constexpr (OBS) {
+    if (frozen) {
+      // A frozen scene: (q, t, m, v) of its objects pass through with the bits of the last applied step -- the
+      // designated workgroup stores them into the output copy, so the ping-pong stays consistent -- and a.Rt keeps
+      // that step's R|t.  No losses / traj row, no points binned: the tiles of its grids find empty bins.  What the
+      // sum kernels then leave in the accumulators and maxima of its objects (1 / M of an empty grid is not finite)
+      // is never read: a frozen scene gathers nothing, and scenes share no accumulator row, maximum or bin.
+      if (e2.w == 0) return;
+      __syncthreads();  // s_state
+      if (threadIdx.x < kStateFloats) {
+        const int i = threadIdx.x;
+        const float x = s_state[i];
+        if (i < 4) sp.q_out[4 * j + i] = x;
+        else if (i < 7) sp.t_out[3 * j + i - 4] = x;
+        else if (i < 14) sp.m_out[7 * j + i - 7] = x;
+        else sp.v_out[7 * j + i - 14] = x;
+      }
+      if (threadIdx.x == 0 && j == e2.x) icc_obs_keep(ob, a.S, e2.z);
+      icc_bin_empties(a, sp, j, nb);
+      return;
+    }
+  }
   if (sp.mode != 0) {
     // the previous iteration's reduced sums of object j (fixed point)
     if (sp.fused)
@@ -96,25 +137,16 @@ __global__ __launch_bounds__(kBinThreads) void k_icc_bin(IccArgs a, IccStepArgs 
       for (int i = 0; i < 7; ++i) { sp.m_out[7 * j + i] = st_new[7 + i]; sp.v_out[7 * j + i] = st_new[14 + i]; }
 #pragma unroll
       for (int i = 0; i < 12; ++i) a.Rt[12 * j + i] = Rt[i];
-      if (sp.traj) {
+      bool stops = false;  // (a scene that freezes with this step has no traj row for it: the fixed loop of as many steps has none)
+      if constexpr (OBS) stops = icc_obs_advance(ob, a.S, e2.z, loss, sp.it, j == e2.x);
+      if (sp.traj && !stops) {
         float *tr = sp.traj + ((int64_t)sp.it * a.O + j) * 7;
 #pragma unroll
         for (int i = 0; i < 7; ++i) tr[i] = st_new[i];
       }
       if (sp.loss_out && j == e2.x) sp.loss_out[e2.z] = loss;
     }
-    if (e2.w != 0) {
-      // ... and empties, all lanes together (one lane storing ~300 words in a row measured 4 us):
-      // this object's accumulators and maxima of the parity the coming iteration adds into, and
-      // the bins of its two grids that the NEXT iteration fills
-      if (threadIdx.x < 2) a.Mbits[(int64_t)(sp.par ^ 1) * 2 * a.O + 2 * j + threadIdx.x] = 0;
-      long long *own = a.acc_own + ((int64_t)(sp.par ^ 1) * a.O + j) * kOwnSlots;
-      for (int i = threadIdx.x; i < kOwnSlots; i += kBinThreads) own[i] = 0;
-      long long *oth = a.acc_oth + ((int64_t)(sp.par ^ 1) * a.O + j) * a.max_ns * 12;
-      for (int i = threadIdx.x; i < a.max_ns * 12; i += kBinThreads) oth[i] = 0;
-      for (int i = threadIdx.x; i < 2 * nb; i += kBinThreads)
-        a.bin_cnt[((int64_t)(sp.cpar ^ 1) * 2 * a.O + 2 * j) * nb + i] = 0u;
-    }
+    if (e2.w != 0) icc_bin_empties(a, sp, j, nb);  // ... and empties
   }
   const float R0 = r0.x, R1 = r0.y, R2 = r0.z, R3 = r0.w, R4 = r1.x, R5 = r1.y, R6 = r1.z,
               R7 = r1.w, R8 = r2.x, T0 = r2.y, T1 = r2.z, T2 = r2.w;

@@ -143,6 +143,33 @@ struct IccStepArgs {
   float *traj;                             // [n_iter][O][7] or NULL
 };
 
+// ---- the per-scene loss observer of mf_icc_refine_converge (the LossObserver of the reference's ROS node,
+// ros/.../collision_based_pose_refinement.py:18-45, next to the optimiser step) ----------------------------------
+// One record per scene and parity copy, in a buffer of the caller's (mf_icc_observer_bytes).  The launch that
+// computes step k reads the copy launch k - 1 wrote and writes the other one: workgroups of one launch are not
+// ordered, so every one of them sees the same `frozen` flag and the same window, whoever runs first.
+constexpr int kObsMaxWindow = 16;
+struct IccObsRec {
+  double delta[kObsMaxWindow];  // ring of the most recent |last - loss|: slots [0, fill), the oldest at `head` once full
+  float last;                   // the loss of the previous step (valid when has_last)
+  int32_t has_last, fill, head;
+  int32_t n_passed;             // steps in a row whose whole window was finite and below the threshold
+  int32_t frozen;               // converged: no object of the scene takes another step
+  int32_t n_steps;              // optimiser steps applied to the scene so far
+  int32_t pad_;
+};
+static_assert(sizeof(IccObsRec) == 8 * kObsMaxWindow + 32, "IccObsRec: mf_icc_observer_bytes counts these bytes");
+struct IccObsArgs {
+  IccObsRec *rec;      // [2 copies][S]
+  int32_t *n_steps;    // [S]: written by the last step of the call
+  double max_delta;    // a delta passes when it is finite and < this (compared in double)
+  int window, n_pass;  // deltas kept (<= kObsMaxWindow); passes in a row that freeze a scene
+  int in;              // the copy this launch reads; it writes copy in ^ 1
+};
+struct IccNoObs {};    // what the kernels without an observer are handed instead
+template <bool OBS> struct IccObsOf { using type = IccNoObs; };
+template <> struct IccObsOf<true> { using type = IccObsArgs; };
+
 constexpr int kTileThreads = 512;
 constexpr int kTileKeep = 4;  // records per lane kept in registers over both passes
 constexpr int kTileR = 4;     // records in flight per lane beyond those

@@ -97,6 +97,17 @@ __global__ __launch_bounds__(256) void k_icc_pose(IccArgs a, const float *__rest
   }
 }
 
+// First node of mf_icc_refine_converge's graph: fresh loss observers (both copies of every scene's record).
+__global__ __launch_bounds__(64) void k_icc_obs_reset(IccObsRec *rec, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  IccObsRec r;
+  for (int k = 0; k < kObsMaxWindow; ++k) r.delta[k] = 0.0;
+  r.last = 0.0f;
+  r.has_last = r.fill = r.head = r.n_passed = r.frozen = r.n_steps = r.pad_ = 0;
+  rec[i] = r;
+}
+
 // Once per batch: bin capacities/offsets per grid and the (target, source, point chunk) table.
 __global__ __launch_bounds__(256) void k_icc_tables(IccArgs a) {
   __shared__ int s_tab_base[1];

@@ -220,4 +220,52 @@ __device__ __forceinline__ void icc_step_lanes(const float *sv, float S_t, const
   for (int i = 0; i < 3; ++i) Rt_out[9 + i] = so[4 + i];
 }
 
+// ---- the loss observer of a scene, advanced by the loss of the step just applied (mf_icc_refine_converge) --------
+// The node's rule: from the second loss on |last - loss| (in double, of the two float32 losses) enters a window of the
+// `window` most recent deltas; while the window is not empty a step passes when every delta in it is below max_delta,
+// n_passed counts passes in a row, and the scene is frozen once n_passed >= n_pass.  A non-finite delta in the window
+// fails the step (Python's max() over a list holding a NaN depends on the order; this rule does not).
+// A pure function of the record launch k - 1 left and of the loss, which every workgroup of the scene computes with
+// the same bits: every designated workgroup evaluates it (a scene that freezes with this step writes no traj row for
+// it), the one of the scene's first object (`store`) writes the record of the other copy.  Returns the new flag.
+__device__ __forceinline__ bool icc_obs_advance(const IccObsArgs &ob, int S, int sc, float loss, int steps, bool store) {
+  const IccObsRec *in = ob.rec + (int64_t)ob.in * S + sc;
+  IccObsRec *out = ob.rec + (int64_t)(ob.in ^ 1) * S + sc;
+  int fill = in->fill, head = in->head, n_passed = in->n_passed;
+  int put = -1;
+  double delta = 0.0;
+  if (in->has_last) {
+    delta = fabs((double)in->last - (double)loss);
+    put = head;
+    head = head + 1 < ob.window ? head + 1 : 0;
+    fill = min(fill + 1, ob.window);
+  }
+  bool pass = true;
+  for (int i = 0; i < kObsMaxWindow; ++i) {
+    const double d = i == put ? delta : in->delta[i];
+    if (i < fill) pass = pass && fabs(d) <= 1.7976931348623157e308 && d < ob.max_delta;  // (finite, below)
+    if (store) out->delta[i] = d;
+  }
+  if (fill > 0) n_passed = pass ? n_passed + 1 : 0;
+  const bool frozen = n_passed >= ob.n_pass;
+  if (store) {
+    out->last = loss;
+    out->has_last = 1;
+    out->fill = fill;
+    out->head = head;
+    out->n_passed = n_passed;
+    out->frozen = frozen ? 1 : 0;
+    out->n_steps = steps;
+    out->pad_ = 0;
+  }
+  return frozen;
+}
+
+// a frozen scene's record goes to the other copy as it is
+__device__ __forceinline__ void icc_obs_keep(const IccObsArgs &ob, int S, int sc) {
+  const IccObsRec *in = ob.rec + (int64_t)ob.in * S + sc;
+  IccObsRec *out = ob.rec + (int64_t)(ob.in ^ 1) * S + sc;
+  *out = *in;
+}
+
 }  // namespace

@@ -10,7 +10,9 @@ namespace {
 
 // ---- the step as a kernel of its own: one 64-lane workgroup per object ----------------
 // mode 1: after the last iteration of mf_icc_refine.  mode 2: mf_icc_loss_grad (loss, gq, gt).
-__global__ __launch_bounds__(64) void k_icc_step(IccArgs a, IccStepArgs sp) {
+// OBS: the last step of mf_icc_refine_converge -- observer as in k_icc_bin<true>, and the scene's step count goes out.
+template <bool OBS>
+__global__ __launch_bounds__(64) void k_icc_step(IccArgs a, IccStepArgs sp, typename IccObsOf<OBS>::type ob) {
   __shared__ float s_sum[kStepSums], s_state[kStateFloats];
   __shared__ long long s_raw[kStepRawWords];
   const int j = blockIdx.x;
@@ -23,6 +25,25 @@ __global__ __launch_bounds__(64) void k_icc_step(IccArgs a, IccStepArgs sp) {
                  : (sp.mode == 1 ? (i < 14 ? sp.m_in[7 * j + i - 7] : sp.v_in[7 * j + i - 14]) : 0.0f);
   }
   const float S_t = a.St[sc];
+  if constexpr (OBS) {
+    const IccObsRec *rec = ob.rec + (int64_t)ob.in * a.S + sc;
+    if (rec->frozen != 0) {  // block-uniform: the state passes through (see k_icc_bin), a.Rt stays
+      __syncthreads();
+      if (threadIdx.x < kStateFloats) {
+        const int i = threadIdx.x;
+        const float x = s_state[i];
+        if (i < 4) sp.q_out[4 * j + i] = x;
+        else if (i < 7) sp.t_out[3 * j + i - 4] = x;
+        else if (i < 14) sp.m_out[7 * j + i - 7] = x;
+        else sp.v_out[7 * j + i - 14] = x;
+      }
+      if (threadIdx.x == 0 && j == ja) {
+        icc_obs_keep(ob, a.S, sc);
+        ob.n_steps[sc] = rec->n_steps;
+      }
+      return;
+    }
+  }
   if (sp.fused)
     icc_step_gather_fused<64>(a, sp.par, j, ja, Ns, s_raw, s_sum);
   else
@@ -35,6 +56,12 @@ __global__ __launch_bounds__(64) void k_icc_step(IccArgs a, IccStepArgs sp) {
   if (threadIdx.x != 0) return;
   const float *st_new = s_x + 12;
   if (sp.loss_out && j == ja) sp.loss_out[sc] = loss;
+  if constexpr (OBS) {
+    if (j == ja) {
+      icc_obs_advance(ob, a.S, sc, loss, sp.it, true);
+      ob.n_steps[sc] = sp.it;
+    }
+  }
   if (sp.mode == 1) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) sp.q_out[4 * j + i] = st_new[i];
