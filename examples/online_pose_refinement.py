@@ -1,0 +1,95 @@
+"""The online path of the reference's ROS nodes on one synthetic sequence: RGB-D frames from a moving camera ->
+InstanceTracker (stable ids) -> OctomapServer.insert_scan (one shared free set in the background map, hit-only instance
+maps) -> OctomapServer.publish_grids (the grids of every instance in the SENSOR frame) -> Model.predict with the
+server's pitch, origin and grid_nontarget_empty -> IterativeCollisionCheckLink.refine_until_converged on the float
+grid_target / grid_noentry, as collision_based_pose_refinement.py passes them.  The network is untrained unless
+--model is given and the CAD clouds / signed distances are stand-ins, as in the other examples; the poses are printed
+before and after the refinement.
+
+    python examples/online_pose_refinement.py [--frames 3] [--model <chainer .npz checkpoint>]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import morefusion_amd as morefusion  # noqa: E402
+from morefusion_amd.contrib.singleview_3d.models import Model  # noqa: E402
+from morefusion_amd.contrib.singleview_3d.models.model import PitchTableModels  # noqa: E402
+
+# the synthetic objects are 30 .. 100 pixels across: the reference's vetoes (40 / 80 / 60) scaled to them
+THRESHOLDS = dict(min_mask=20, min_bbox=30, min_side=24)
+# the synthetic scene has its table top at y = 0.2 with y pointing down: the server's map frame has it at z = 0, z up
+TO_GROUND = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0.2], [0, 0, 0, 1]], np.float64)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=3)
+    ap.add_argument("--model", help="chainer .npz checkpoint of the reference")
+    args = ap.parse_args()
+    frames = morefusion.synthetic.make_tracking_sequence(0, args.frames)
+    models = PitchTableModels()
+    pitch_of = lambda c: models.get_voxel_pitch(32, int(c))  # noqa: E731
+    to_gpu = lambda x: torch.as_tensor(x).cuda()  # noqa: E731
+    rs = np.random.RandomState(0)
+    cad = {}  # stand-in model clouds and signed distances: a sphere / a box of the class's size
+
+    def cad_of(c):
+        if c not in cad:
+            points = morefusion.synthetic.make_primitive("sphere" if c % 2 else "box", pitch_of(c), rs)[0]
+            cad[c] = (points.astype(np.float32), morefusion.synthetic.synthetic_sdf(points).astype(np.float32))
+        return cad[c]
+
+    torch.manual_seed(0)
+    model = Model(n_fg_class=21, with_occupancy=True)
+    if args.model:
+        morefusion.serializers.load_npz(args.model, model)
+    model = model.cuda().eval()
+    server = morefusion.contrib.OctomapServer()
+    tracker = morefusion.contrib.InstanceTracker(server.mapping, thresholds=THRESHOLDS)
+    for k, f in enumerate(frames):
+        K, T = f["K"], TO_GROUND @ f["T_sensor_to_map"]
+        pcd = morefusion.geometry.pointcloud_from_depth(f["depth"], K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+        tracked, _, class_of, _ = tracker.track(to_gpu(pcd.astype(np.float32)), to_gpu(f["label_detected"]),
+                                                f["class_ids_by_detection"], K, T)
+        server.insert_scan(tracker.pts_map.reshape(pcd.shape), tracked, class_of, pitch_of, origin=T[:3, 3])
+        grids = server.publish_grids(T)
+        print(f"frame {k}: maps {server.mapping.instance_ids}, published {grids['instance_ids']}")
+    # the pose stage of the last frame, in the sensor frame: crops -> the server's grids -> the network
+    published = grids["instance_ids"]
+    crops = morefusion.geometry.instance_crops(to_gpu(f["rgb"]), to_gpu(f["depth"]), K, tracked,
+                                               np.array(published, np.int32), image_size=256, min_valid=50)
+    keep = crops["keep"]
+    if int(keep.sum()) == 0:
+        print("no instance with enough valid pixels in the last frame")
+        return
+    ids = [i for i, ok in zip(published, keep.cpu().tolist()) if ok]
+    class_id = torch.tensor(grids["class_ids"], dtype=torch.int32).cuda()[keep]
+    pitch, origin = grids["pitch"][keep], grids["origin"][keep].float()
+    with torch.no_grad():
+        quaternion, translation, confidence = model.predict(
+            class_id=class_id, rgb=crops["rgb"][keep], pcd=crops["pcd"][keep], pitch=pitch, origin=origin,
+            grid_nontarget_empty=grids["grid_nontarget_empty"][keep])
+    best = confidence.argmax(dim=1)
+    ar = torch.arange(len(ids), device=best.device)
+    T_init = morefusion.functions.transformation_matrix(quaternion[ar, best], translation[ar, best]).cpu().numpy()
+    # collision_based_pose_refinement.py:86-98: the float grids as the server publishes them
+    points = [to_gpu(cad_of(c)[0]) for c in class_id.tolist()]
+    sdf = [to_gpu(cad_of(c)[1]) for c in class_id.tolist()]
+    link = morefusion.contrib.IterativeCollisionCheckLink(T_init, sdf_offset=0.01).to_gpu()
+    n_steps = link.refine_until_converged(points, sdf, pitch, origin, grids["grid_target"][keep],
+                                          grids["grid_noentry"][keep], sync=True)
+    T_refined = morefusion.functions.transformation_matrix(link.quaternion, link.translation).detach().cpu().numpy()
+    print(f"refined {len(ids)} objects in {int(n_steps[0])} steps (of at most 30)")
+    for i, a, b in zip(ids, T_init, T_refined):
+        q0, q1 = morefusion.geometry.quaternion_from_matrix(a), morefusion.geometry.quaternion_from_matrix(b)
+        print(f"instance {i}: before t = {np.round(a[:3, 3], 4).tolist()} q = {np.round(q0, 4).tolist()}, "
+              f"after t = {np.round(b[:3, 3], 4).tolist()} q = {np.round(q1, 4).tolist()}")
+
+
+if __name__ == "__main__":
+    main()

@@ -914,6 +914,56 @@ int mf_occtrack_merge(const int32_t *label_reference, const int32_t *label_track
                       const int32_t *ref_ids, int32_t n_ref, void *workspace, int32_t *label_merged,
                       mfStream_t stream);
 
+/* ---- map server: insert and grid publication (contrib/octomap_server.py, csrc/occserver.hip) --
+ * OctomapServer::insertScan / publishGrids of the reference's ROS node over the mfOccTree boxes
+ * (DESIGN.md "Map server").  Only the stride-2 pixels (even row and even column) of the [H, W]
+ * frame with a non-NaN point take part.  `slots` [n_slots, 3] int32 = {label value, tree index,
+ * unused}: the tree that takes a label's end points (the background's label -1 included);
+ * `bg_tree`: the tree that takes the frame's one free set.  Labels: >= 0 an instance id, -1
+ * background, -2 uncertain (its rays still free the background).  Every call is asynchronous,
+ * allocates nothing and never synchronises; no float atomics, all results are bitwise independent
+ * of the order in which lanes run. */
+/* bounds [n_trees, 6] int32 := per tree {min key x,y,z, max key x,y,z}: bg_tree over every valid
+ * point whatever its label, any other tree over the points of its own label ({INT_MAX x3,
+ * INT_MIN x3} without points); 1 <= n_trees <= 256. */
+int mf_occserver_bounds(const float *pts, const int32_t *label, int32_t H, int32_t W, const int32_t *slots,
+                        int32_t n_slots, const mfOccTree *trees, int32_t bg_tree, int32_t n_trees,
+                        int32_t *bounds, mfStream_t stream);
+/* table [n_slots + 1, 10] float64: per slot, over its label's valid stride-2 points without the
+ * one of the smallest pixel index, {count, centroid x,y,z, min x,y,z, max x,y,z} (all zero when
+ * count == 0).  Min / max are exact float32 values.  The centroid is float32(sum / count) of
+ * float64 sums taken in one fixed order: lane t of 1024 adds its stride-2 pixels t, t + 1024, ...
+ * in ascending order, then lanes fold pairwise (t += t + off, off = 512 .. 1).  Row n_slots,
+ * column 0: the smallest label >= 0 of the whole image that has no slot, or -1. */
+int mf_occserver_stats(const float *pts, const int32_t *label, int32_t H, int32_t W, const int32_t *slots,
+                       int32_t n_slots, double *table, mfStream_t stream);
+/* Per valid stride-2 pixel: the computeRayKeys DDA origin -> point sets bit 0 of the free word in
+ * bg_tree; a label != -2 with a slot sets bit 0 of the occupied word at the end key of its tree;
+ * a label != -1 sets the free bit of bg_tree at the end key.  Keys outside a box are dropped and
+ * counted in *overflow (may be NULL). */
+int mf_occserver_raycast(const float *pts, const int32_t *label, int32_t H, int32_t W, const int32_t *slots,
+                         int32_t n_slots, const mfOccTree *trees, int32_t bg_tree, float origin_x,
+                         float origin_y, float origin_z, int32_t *overflow, mfStream_t stream);
+/* One lane per cell of every tree: occupied bit -> l + hit, else free bit -> l + miss (float32,
+ * unknown cells start at 0), clamped to [lo_min, lo_max]; then the bits are cleared. */
+int mf_occserver_apply(const mfOccTree *trees, int32_t n_trees, int64_t max_cells, float hit, float miss,
+                       float lo_min, float lo_max, mfStream_t stream);
+/* publishGrids for B grids of D^3 voxels in the SENSOR frame.  Per grid: centre = T_map_to_sensor
+ * applied to center_map[b] (float32, ((T0 x + T1 y) + T2 z) + T3, no contraction); origin[b] :=
+ * double(centre) - (D / 2.0 - 0.5) * double(pitch[b]); voxel centre = float32(origin + double(
+ * pitch[b] * float(i))) per axis, moved to the map frame by T_sensor_to_map (same convention) and
+ * searched as a float32 point.  flags & 1: map z < 0 -> noentry = float32(prob_max) and nothing
+ * else.  Own tree (target_tree[b]) known with occupancy > 0.5 -> grid_target = float32(occupancy);
+ * otherwise every other tree of `order` [n_trees] (tree indices in ascending instance id) that is
+ * known: bg_tree with flags & 2 and occupancy < 0.5 -> noentry = float32(1 - occupancy), else
+ * occupancy >= prob_max (in double) -> noentry = float32(occupancy); the last writer wins.
+ * grid_nontarget_empty (uint8) := noentry != 0.  Both T are row-major [4, 4] float32, DEVICE. */
+int mf_occserver_publish(const mfOccTree *trees, int32_t n_trees, const int32_t *order, int32_t bg_tree,
+                         const int32_t *target_tree, const float *pitch, const float *center_map,
+                         const float *T_map_to_sensor, const float *T_sensor_to_map, double prob_max,
+                         int32_t flags, int32_t B, int32_t D, double *origin, float *grid_target,
+                         float *grid_noentry, uint8_t *grid_nontarget_empty, mfStream_t stream);
+
 /* ---- point-to-point ICP registration (contrib/icp_registration.py, csrc/icpreg.hip) ---------
  * open3d's voxel_down_sample + registration_icp(PointToPoint, no scaling), restated in float64
  * (DESIGN.md "ICP registration").  Point sets are packed double [n, 3] rows with int64 [n_sets + 1]

@@ -221,6 +221,11 @@ _SIGNATURES = {
     "mf_occtrack_relabel": ([_p, _p, _i, _i, _p, _i, _p, _i] + [_p] * 5, _i),
     "mf_occtrack_clean": ([_p] + [_i] * 4 + [_p, _p, _p], _i),
     "mf_occtrack_merge": ([_p, _p, _i, _i, _p, _i, _p, _p, _p], _i),
+    "mf_occserver_bounds": ([_p, _p, _i, _i, _p, _i, _p, _i, _i, _p, _p], _i),
+    "mf_occserver_stats": ([_p, _p, _i, _i, _p, _i, _p, _p], _i),
+    "mf_occserver_raycast": ([_p, _p, _i, _i, _p, _i, _p, _i, _f, _f, _f, _p, _p], _i),
+    "mf_occserver_apply": ([_p, _i, _i64, _f, _f, _f, _f, _p], _i),
+    "mf_occserver_publish": ([_p, _i, _p, _i] + [_p] * 5 + [_d, _i, _i, _i] + [_p] * 5, _i),
     "mf_icpreg_workspace_bytes": ([_i64, _i64, _i64], _i64),
     "mf_icpreg_bounds": ([_p, _p, _i, _d, _p, _p, _p], _i),
     "mf_icpreg_prepare": ([_p, _p, _i, _d, _p, _p, _p, _i64, _p, _p, _i64, _d, _i64] + [_p] * 7, _i),

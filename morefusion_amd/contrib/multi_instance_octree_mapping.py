@@ -260,13 +260,17 @@ class MultiInstanceOctreeMapping:
         _lib.check(L.mf_occmap_bounds(pts.data_ptr(), label.data_ptr(), pts.shape[0], st.data_ptr(), len(slots),
                                       table.data_ptr(), n_trees, bounds.data_ptr(), _lib.stream_ptr()),
                    "mf_occmap_bounds")
-        bounds = bounds.cpu().numpy()
+        self._fit(bounds.cpu().numpy(), origin)
+
+    def _fit(self, bounds, origin, origin_trees=None):
+        """Grow every box that the key bounds [n_trees, 6] of a batch leave; ``origin``'s key joins the bounds of the
+        trees in ``origin_trees`` (tree indices; None: every tree with points)."""
         changed = False
         for t, tree in enumerate(self._trees.values()):
             lo, hi = bounds[t, :3].astype(np.int64), bounds[t, 3:].astype(np.int64)
             if (lo > hi).any():
                 continue  # no point of this tree in the batch
-            if origin is not None:
+            if origin is not None and (origin_trees is None or t in origin_trees):
                 ok = [_key(c, tree.res_factor) for c in _lib.as_float3(origin)]
                 if None not in ok:
                     lo, hi = np.minimum(lo, ok), np.maximum(hi, ok)
