@@ -6,7 +6,11 @@ grid_target / grid_noentry, as collision_based_pose_refinement.py passes them.  
 --model is given and the CAD clouds / signed distances are stand-ins, as in the other examples; the poses are printed
 before and after the refinement.
 
-    python examples/online_pose_refinement.py [--frames 3] [--model <chainer .npz checkpoint>]
+    python examples/online_pose_refinement.py [--frames 3] [--model <chainer .npz checkpoint>] [--render-service]
+
+--render-service: the tracker matches against the reference's render-service route (use_render_service,
+OctomapServer.cpp:126-135) -- OctomapServer.grids_in_map_frame meshed and rasterised (contrib.render_voxel_grids) --
+instead of the per-pixel ray-cast.
 """
 import argparse
 import os
@@ -30,6 +34,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=3)
     ap.add_argument("--model", help="chainer .npz checkpoint of the reference")
+    ap.add_argument("--render-service", action="store_true", help="render the maps as meshes (render_voxel_grids.py)")
     args = ap.parse_args()
     frames = morefusion.synthetic.make_tracking_sequence(0, args.frames)
     models = PitchTableModels()
@@ -50,15 +55,19 @@ def main():
         morefusion.serializers.load_npz(args.model, model)
     model = model.cuda().eval()
     server = morefusion.contrib.OctomapServer()
-    tracker = morefusion.contrib.InstanceTracker(server.mapping, thresholds=THRESHOLDS)
+    if args.render_service:
+        tracker = morefusion.contrib.InstanceTracker(server.mapping, thresholds=THRESHOLDS, render="mesh", server=server)
+    else:
+        tracker = morefusion.contrib.InstanceTracker(server.mapping, thresholds=THRESHOLDS)
     for k, f in enumerate(frames):
         K, T = f["K"], TO_GROUND @ f["T_sensor_to_map"]
         pcd = morefusion.geometry.pointcloud_from_depth(f["depth"], K[0, 0], K[1, 1], K[0, 2], K[1, 2])
         tracked, _, class_of, _ = tracker.track(to_gpu(pcd.astype(np.float32)), to_gpu(f["label_detected"]),
-                                                f["class_ids_by_detection"], K, T)
+                                                f["class_ids_by_detection"], K, T,
+                                                depth=to_gpu(f["depth"]) if args.render_service else None)
         server.insert_scan(tracker.pts_map.reshape(pcd.shape), tracked, class_of, pitch_of, origin=T[:3, 3])
         grids = server.publish_grids(T)
-        print(f"frame {k}: maps {server.mapping.instance_ids}, published {grids['instance_ids']}")
+        print(f"frame {k} ({tracker.render}): maps {server.mapping.instance_ids}, published {grids['instance_ids']}")
     # the pose stage of the last frame, in the sensor frame: crops -> the server's grids -> the network
     published = grids["instance_ids"]
     crops = morefusion.geometry.instance_crops(to_gpu(f["rgb"]), to_gpu(f["depth"]), K, tracked,

@@ -1258,6 +1258,57 @@ int mf_occreg_refine(const mfOccRegBatch *batch, float *q, float *t, float *adam
                      int32_t step0, float alpha_q, float alpha_t, float *losses, float *traj, void *workspace,
                      mfStream_t stream);
 
+/* ---- occupancy grids -> welded, smoothed triangle meshes (geometry/grid_mesh.py, csrc/gridmesh.hip) ----------
+ * grid_msg_to_mesh of the reference (ros/src/morefusion_ros/nodes/voxel_grids_to_mesh_markers.py:80-97) for a
+ * batch: the 0.5-level surface of each grid's occupancy (a cell is occupied iff its value is > 0) over the
+ * six-tetrahedra subdivision of the lattice padded by one empty layer, welded, then trimesh's Humphrey filter
+ * (DESIGN.md "Grid meshes"; tests/gridmesh_ref.py is the NumPy mirror, bit for bit).  Grid b: the X Y Z floats at
+ * grid_off[b] of `grids`, dims[b] = (X, Y, Z) each in 1 .. MF_GRIDMESH_MAX_DIM (a grid with other dims is empty);
+ * vertex = origin[b] + pitch[b] ((pa + pb) / 2 - 1) in float64 for the lattice edge pa-pb.  Vertex and face order
+ * are fixed by the input alone (header of csrc/gridmesh.hip).  All arrays are DEVICE arrays; every call is
+ * asynchronous on `stream`, allocates nothing and never synchronises.  Refusals return < 0. */
+#define MF_GRIDMESH_MAX_DIM 32
+#define MF_GRIDMESH_MAX_GRIDS 4096
+#define MF_GRIDMESH_MAX_NEIGHBOURS 12 /* faces (= neighbours) at a vertex of such a surface, at most */
+#define MF_GRIDMESH_MAX_ROWS 1073741824 /* vertices, and faces, of a batch */
+/* Host-only: bytes (16-byte aligned parts) of the workspace of mf_gridmesh_count / _emit for n_grids grids plus the
+ * one of mf_gridmesh_smooth for n_vertices vertices; < 0 past the caps above. */
+int64_t mf_gridmesh_workspace_bytes(int64_t n_grids, int64_t n_vertices);
+/* Count: offsets int64 [2, n_grids + 1] = the vertices (row 0) and faces (row 1) before each grid, the totals last.
+ * The caller reads it back to size the buffers of mf_gridmesh_emit; `workspace` keeps the per-layer offsets. */
+int mf_gridmesh_count(const float *grids, const int64_t *grid_off, const int32_t *dims, int32_t n_grids,
+                      void *workspace, int64_t *offsets, mfStream_t stream);
+/* Emit: vertices float64 [n_vertices, 3], faces int32 [n_faces, 3] (indices local to their mesh), packed in grid
+ * order; n_vertices / n_faces are the totals of `offsets` (rows past them are not written). */
+int mf_gridmesh_emit(const float *grids, const int64_t *grid_off, const int32_t *dims, const double *pitch,
+                     const double *origin, int32_t n_grids, const void *workspace, const int64_t *offsets,
+                     int64_t n_vertices, int64_t n_faces, double *vertices, int32_t *faces, mfStream_t stream);
+/* Neighbour rows of packed meshes (offsets as above): vertex a's row neighbours[12 a ..] = the heads b of the
+ * directed half-edges a -> b of its faces, as packed vertex indices in ascending order, -1 behind them;
+ * degree [n_vertices] = their number (a count above 12 marks a vertex that the filter leaves in place). */
+int mf_gridmesh_adjacency(const int32_t *faces, const int64_t *offsets, int32_t n_grids, int64_t n_vertices,
+                          int64_t n_faces, int32_t *neighbours, int32_t *degree, mfStream_t stream);
+/* trimesh.smoothing.filter_humphrey with the equal-weight Laplacian L (mean over a row, summed in ascending
+ * neighbour index), `iterations` times in place: q = v; v = L q; b = v - (alpha v0 + (1 - alpha) q);
+ * v = v - (beta b + (1 - beta) L b), v0 the vertices at entry.  workspace: the smooth part of
+ * mf_gridmesh_workspace_bytes(0, n_vertices). */
+int mf_gridmesh_smooth(double *vertices, const int32_t *neighbours, const int32_t *degree, int64_t n_vertices,
+                       double alpha, double beta, int32_t iterations, void *workspace, mfStream_t stream);
+/* The label test of the reference's render service (nodes/render_voxel_grids.py:66-99): label = instance where
+ * something was drawn (instance != -1) and -2 elsewhere, -2 too where depth_rendered > depth_sensor + 0.01
+ * (float32; false for a NaN reading).  Images [height, width]. */
+int mf_gridmesh_label(const float *depth_rendered, const int32_t *instance, const float *depth_sensor,
+                      int32_t height, int32_t width, int32_t *label, mfStream_t stream);
+
+/* ---- the map server's grids in the map frame (contrib/octomap_server.py, csrc/occserver.hip) --------------
+ * OctomapServer::getGridsInWorldFrame (OctomapServer.cpp:456-508): grid b = the D^3 samples around center_map[b] of
+ * tree target_tree[b]: origin[b] = double(center) - (D / 2 - 0.5) double(pitch[b]) (float64 [B, 3], written),
+ * sample = origin + double(pitch * float(index)) searched as a float64 coordinate; grid = float32(occupancy) where
+ * the node exists and its occupancy is > 0.5, else 0. */
+int mf_occserver_map_grids(const mfOccTree *trees, int32_t n_trees, const int32_t *target_tree, const float *pitch,
+                           const float *center_map, int32_t B, int32_t D, double *origin, float *grid,
+                           mfStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

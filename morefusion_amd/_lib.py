@@ -255,6 +255,13 @@ _SIGNATURES = {
     "mf_occreg_workspace_bytes": ([_i64, _i64, _i64], _i64),
     "mf_occreg_loss_grad": ([_p] * 8, _i),  # (mfOccRegBatch by reference: ctypes.byref(OccRegBatch))
     "mf_occreg_refine": ([_p] * 5 + [_i, _i, _f, _f] + [_p] * 4, _i),
+    "mf_gridmesh_workspace_bytes": ([_i64, _i64], _i64),
+    "mf_gridmesh_count": ([_p, _p, _p, _i, _p, _p, _p], _i),
+    "mf_gridmesh_emit": ([_p] * 5 + [_i, _p, _p, _i64, _i64, _p, _p, _p], _i),
+    "mf_gridmesh_adjacency": ([_p, _p, _i, _i64, _i64, _p, _p, _p], _i),
+    "mf_gridmesh_smooth": ([_p, _p, _p, _i64, _d, _d, _i, _p, _p], _i),
+    "mf_gridmesh_label": ([_p, _p, _p, _i, _i, _p, _p], _i),
+    "mf_occserver_map_grids": ([_p, _i, _p, _p, _p, _i, _i, _p, _p, _p], _i),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

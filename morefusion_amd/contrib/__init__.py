@@ -9,7 +9,7 @@ from . import singleview_3d
 from . import singleview_pcd
 from .multi_instance_octree_mapping import MultiInstanceOctreeMapping
 from .icp_registration import ICPRegistration, icp_registration_batch
-from .instance_tracking import InstanceTracker, render_instance_maps, track_instance_ids
+from .instance_tracking import InstanceTracker, render_instance_maps, render_voxel_grids, track_instance_ids
 from .object_mapping import ObjectMapping
 from .picking_order import SelectPickingOrder, get_picking_order, occlusion_analysis, quaternion_from_two_vectors
 from .octomap_server import OctomapServer

@@ -84,6 +84,29 @@ def render_instance_maps(mapping, pts_map, K, T_sensor_to_map, height, width, in
     return label, depth
 
 
+def render_voxel_grids(grids, depth, K, T_sensor_to_map, height, width):
+    """The reference's render service (ros/src/morefusion_ros/nodes/render_voxel_grids.py): ``grids`` (the dict of
+    ``OctomapServer.grids_in_map_frame``) -> meshes (``geometry.voxel_grids_to_meshes``) -> one composite render seen
+    through the inverse of ``T_sensor_to_map`` with the instance ids (``geometry.render_meshes``) -> the label test
+    against the sensor ``depth`` [H,W] float32 (NaN = no reading) with its 1 cm margin.  Returns the [H,W] int32 device
+    label: the instance id, -2 where nothing was drawn or the surface lies behind the reading.  A grid without an
+    occupied cell is skipped (:61-62); with none left every pixel is -2."""
+    from ..geometry import grid_mesh, render_meshes
+    H, W = int(height), int(width)
+    grid = grids["grid"]
+    dev = grid.device if isinstance(grid, torch.Tensor) else torch.device("cuda")
+    meshes = grid_mesh.voxel_grids_to_meshes(grid, grids["pitch"], grids["origin"], device=dev)
+    keep = [i for i, (_, f) in enumerate(meshes) if f.shape[0]]
+    if not keep:
+        return torch.full((H, W), -2, dtype=torch.int32, device=dev)
+    T = np.asarray(T_sensor_to_map.cpu() if isinstance(T_sensor_to_map, torch.Tensor) else T_sensor_to_map, np.float64)
+    T_map_to_sensor = np.linalg.inv(T.reshape(4, 4))
+    Kh = np.asarray(K.cpu() if isinstance(K, torch.Tensor) else K, np.float64).reshape(3, 3)
+    out = render_meshes([meshes[i] for i in keep], np.stack([T_map_to_sensor] * len(keep)), Kh, H, W,
+                        instance_ids=[int(grids["instance_ids"][i]) for i in keep], device=dev)
+    return grid_mesh.label_of_render(out["depth"][0], out["instance"][0], depth)
+
+
 def track_instance_ids(label_rendered, label_detected, ref_ids, det_ids, counter, thresholds=None):
     """``track_instance_id`` on two [H,W] int32 device images.  ``ref_ids`` / ``det_ids``: the ids that may occur in
     the rendered / detected image; ``counter``: int32 device tensor [1], advanced in place.  Returns a dict of device
@@ -135,7 +158,15 @@ def track_instance_ids(label_rendered, label_detected, ref_ids, det_ids, counter
 class InstanceTracker:
     """Carries instance ids from frame to frame over a ``MultiInstanceOctreeMapping``."""
 
-    def __init__(self, mapping, thresholds=None):
+    def __init__(self, mapping, thresholds=None, render="raycast", server=None):
+        """``render="raycast"``: the maps are ray-cast per pixel (``render_instance_maps``).  ``render="mesh"``: the
+        reference's render-service route -- ``server.grids_in_map_frame()`` meshed and rasterised
+        (``render_voxel_grids``); it needs the ``OctomapServer`` that owns ``mapping`` and a ``depth`` in ``track``."""
+        if render not in ("raycast", "mesh"):
+            raise ValueError('render must be "raycast" or "mesh"')
+        if render == "mesh" and (server is None or server.mapping is not mapping):
+            raise ValueError('render="mesh" needs server=, the OctomapServer that owns the mapping')
+        self.render, self.server = render, server
         self.mapping = mapping
         self.thresholds = dict(DEFAULT_THRESHOLDS, **(thresholds or {}))
         first = max([i for i in mapping.instance_ids] + [BACKGROUND_ID]) + 1
@@ -144,9 +175,10 @@ class InstanceTracker:
         self.pts_map = None       # the last frame's points in the map frame, float32 device [H*W, 3]
         self.last = None          # the last frame's track_instance_ids result
 
-    def track(self, pcd, label_detected, class_ids_by_detection, K, T_sensor_to_map):
+    def track(self, pcd, label_detected, class_ids_by_detection, K, T_sensor_to_map, depth=None):
         """One frame: ``pcd`` [H,W,3] in the sensor frame (NaN holes), ``label_detected`` [H,W] the detector's
-        instance label (< 0: none), ``class_ids_by_detection`` {detection id: class id}.  Returns (label_tracked,
+        instance label (< 0: none), ``class_ids_by_detection`` {detection id: class id}; ``depth`` [H,W] float32, the
+        sensor depth (NaN = no reading), for ``render="mesh"`` only.  Returns (label_tracked,
         label_merged, instance_id_to_class_id, label_rendered); the images as NumPy arrays for NumPy inputs, device
         tensors otherwise.  ``self.pts_map`` is what ``integrate_tracked_frame`` takes next."""
         as_tensor = isinstance(pcd, torch.Tensor) or isinstance(label_detected, torch.Tensor)
@@ -157,7 +189,12 @@ class InstanceTracker:
         if self.pts_map.shape[0] != H * W:
             raise ValueError("pcd and label_detected differ in size")
         ref_ids = sorted(i for i in self.mapping.instance_ids if i != BACKGROUND_ID)
-        rendered, _ = render_instance_maps(self.mapping, self.pts_map, K, T_sensor_to_map, H, W, ref_ids)
+        if self.render == "mesh":
+            if depth is None:
+                raise ValueError('render="mesh" needs the sensor depth')
+            rendered = render_voxel_grids(self.server.grids_in_map_frame(), depth, K, T_sensor_to_map, H, W)
+        else:
+            rendered, _ = render_instance_maps(self.mapping, self.pts_map, K, T_sensor_to_map, H, W, ref_ids)
         det = {int(k): int(v) for k, v in dict(class_ids_by_detection).items()}
         out = track_instance_ids(rendered, detected, ref_ids, det, self.counter, self.thresholds)
         remap = out["remap"].cpu().numpy()  # the frame's one read-back: [n_det] tracked ids + the counter

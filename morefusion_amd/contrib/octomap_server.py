@@ -6,7 +6,8 @@
 "Map server: shared free set, hit-only instance maps, grids in the sensor frame" for the model and every precision
 choice.  The online path is frames -> ``InstanceTracker(server.mapping).track`` -> ``server.insert_scan`` ->
 ``server.publish_grids`` -> ``Model.predict`` -> ``IterativeCollisionCheckLink.refine_until_converged``
-(examples/online_pose_refinement.py).
+(examples/online_pose_refinement.py).  ``server.grids_in_map_frame`` feeds the render-service route of the tracker
+(``contrib.render_voxel_grids``, ``InstanceTracker(render="mesh", server=server)``).
 
 Host synchronisation per frame: the key bounds of the scan [n_trees, 6] and the per-instance statistics
 [n_instances + 2, 10], read back together before the ray-cast.  ``publish_grids`` reads nothing back.
@@ -155,6 +156,28 @@ class OctomapServer:
             out["pitch"].data_ptr(), centers.data_ptr(), Ts[0].data_ptr(), Ts[1].data_ptr(), self.prob_max, flags, B,
             _DIM, out["origin"].data_ptr(), out["grid_target"].data_ptr(), out["grid_noentry"].data_ptr(),
             out["grid_nontarget_empty"].data_ptr(), _lib.stream_ptr()), "mf_occserver_publish")
+        return out
+
+    def grids_in_map_frame(self):
+        """``getGridsInWorldFrame`` (OctomapServer.cpp:456-508): for every instance with a centre, in ascending id, the
+        32^3 samples of its OWN map around its centre, in the MAP frame.  -> dict(instance_ids, class_ids (lists),
+        pitch [B] float32, origin [B,3] float64 = centre - 15.5 pitch, grid [B,32,32,32] float32: the occupancy where it
+        is > 0.5, else 0), device tensors.  What ``contrib.render_voxel_grids`` meshes; nothing is read back."""
+        m = self.mapping
+        ids = sorted(i for i in m._trees if i != BACKGROUND_ID and i in self.centers)
+        B = len(ids)
+        dev = self.device
+        out = dict(instance_ids=ids, class_ids=[self.class_ids[i] for i in ids],
+                   pitch=torch.tensor([m._trees[i].resolution for i in ids], dtype=torch.float64).to(torch.float32).to(dev),
+                   origin=torch.zeros((B, 3), dtype=torch.float64, device=dev),
+                   grid=torch.empty((B, _DIM, _DIM, _DIM), dtype=torch.float32, device=dev))
+        if B == 0:
+            return out
+        target = torch.tensor([m._index(i) for i in ids], dtype=torch.int32).to(dev)
+        centers = torch.from_numpy(np.stack([self.centers[i] for i in ids]).astype(np.float32)).to(dev)
+        _lib.check(_lib.lib().mf_occserver_map_grids(
+            m._descs().data_ptr(), len(m._trees), target.data_ptr(), out["pitch"].data_ptr(), centers.data_ptr(), B,
+            _DIM, out["origin"].data_ptr(), out["grid"].data_ptr(), _lib.stream_ptr()), "mf_occserver_map_grids")
         return out
 
     @staticmethod

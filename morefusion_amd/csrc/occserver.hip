@@ -16,7 +16,7 @@
 //   k_srv_raycast  one lane per stride-2 pixel: the shared DDA (occmap_scan.h) into the background's free word,
 //                  the end key into the occupied word of the label's tree;
 //   k_srv_apply    one lane per cell: occupied -> one clamped hit, else free -> one clamped miss; bits cleared.
-// publishGrids: k_srv_publish, one lane per voxel of all B grids.
+// publishGrids: k_srv_publish, one lane per voxel of all B grids; getGridsInWorldFrame (:456-508): k_srv_map_grids.
 // No float atomics; every result is independent of the order in which lanes run.
 #include <limits.h>
 #include <math.h>
@@ -291,6 +291,48 @@ __global__ __launch_bounds__(kThreads) void k_srv_publish(const mfOccTree *__res
   grid_nte[g] = ne != 0.0f;
 }
 
+// getGridsInWorldFrame: one lane per voxel of all B grids; the sample is a float64 coordinate (search(double x, ...))
+__device__ __forceinline__ bool coord_key_f64(double c, double rf, int &key) {
+  const double s = floor(c * rf);
+  if (!(s >= -(double)kKeyMax && s < (double)kKeyMax)) return false;
+  key = (int)s + kKeyMax;
+  return true;
+}
+
+__global__ __launch_bounds__(kThreads) void k_srv_map_grids(const mfOccTree *__restrict__ trees, int n_trees,
+                                                            const int32_t *__restrict__ target_tree,
+                                                            const float *__restrict__ pitch,
+                                                            const float *__restrict__ center_map, int B, int D,
+                                                            double *__restrict__ origin_out, float *__restrict__ grid) {
+  const int64_t nvox = (int64_t)D * D * D;
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= nvox * B) return;
+  const int b = (int)(g / nvox);
+  const int64_t v = g - (int64_t)b * nvox;
+  const int idx[3] = {(int)(v / ((int64_t)D * D)), (int)((v / D) % D), (int)(v % D)};
+  const float p32 = pitch[b];
+  const int target = target_tree[b];
+  bool ok = target >= 0 && target < n_trees;
+  int k[3] = {0, 0, 0};
+  for (int a = 0; a < 3; ++a) {
+    const double origin = (double)center_map[3 * b + a] - ((double)D / 2.0 - 0.5) * (double)p32;
+    if (v == 0) origin_out[3 * b + a] = origin;
+    const double x = origin + (double)(p32 * (float)idx[a]);  // grid.pitch * i: float
+    if (ok) ok = coord_key_f64(x, trees[target].res_factor, k[a]);
+  }
+  float out = 0.0f;
+  if (ok) {
+    const mfOccTree t = trees[target];
+    const int64_t cell = cell_of(t, k[0], k[1], k[2]);
+    const float l = cell < 0 ? __int_as_float(0x7fc00000) : t.logodds[cell];
+    if (!isnan(l)) {
+      const double occ = 1.0 - 1.0 / (1.0 + exp((double)l));
+      if (occ > 0.5) out = (float)occ;
+    }
+  }
+  grid[g] = out;
+}
+
 int bad(const char *what) {
   mf::set_last_error(hipErrorInvalidValue, what);
   return -(int)hipErrorInvalidValue;
@@ -360,4 +402,17 @@ extern "C" int mf_occserver_publish(const mfOccTree *trees, int32_t n_trees, con
                      T_map_to_sensor, T_sensor_to_map, prob_max, (int)flags, (int)B, (int)D, origin, grid_target,
                      grid_noentry, grid_nontarget_empty);
   return mf::check_launch("mf_occserver_publish");
+}
+
+extern "C" int mf_occserver_map_grids(const mfOccTree *trees, int32_t n_trees, const int32_t *target_tree,
+                                      const float *pitch, const float *center_map, int32_t B, int32_t D,
+                                      double *origin, float *grid, mfStream_t stream) {
+  if (B < 0 || D <= 0 || D > 1024 || n_trees <= 0) return bad("mf_occserver_map_grids: bad sizes");
+  const int64_t n = (int64_t)B * D * D * D;
+  if (n == 0) return 0;
+  if ((n + kThreads - 1) / kThreads > INT_MAX) return bad("mf_occserver_map_grids: too many voxels");
+  hipLaunchKernelGGL(k_srv_map_grids, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                     (hipStream_t)stream, trees, (int)n_trees, target_tree, pitch, center_map, (int)B, (int)D, origin,
+                     grid);
+  return mf::check_launch("mf_occserver_map_grids");
 }
