@@ -387,6 +387,12 @@ int mf_interpolate_voxel_grid_cl_split_fwd(const float *vox, const float *points
                                            int64_t los, mfStream_t stream);
 int mf_occupancy_convs_fwd(const float *grid, const float *w1, const float *b1, const float *w2,
                            const float *b2, float *h1, float *h2, int32_t B, int32_t D, mfStream_t stream);
+/* The same with h2's split-bf16 form written by the second convolution's own launch: h2s bf16 [B, D^3, 2 x 16] (a
+ * voxel's 16 hi channels, then its 16 lo channels: the split of the fp32 value h2 gets), the operand of
+ * mf_conv3d_k4s2_split_fwd on conv3's occupancy channels.  h2 may be null (only the split form is written). */
+int mf_occupancy_convs_split_fwd(const float *grid, const float *w1, const float *b1, const float *w2,
+                                 const float *b2, float *h1, float *h2, void *h2s, int32_t B, int32_t D,
+                                 mfStream_t stream);
 
 /* ---- per-point 1x1 convolutions (heads, point MLP) as row-major fp32-MFMA GEMMs ---------------
  * replaces the cuDNN Convolution1D(k = 1) chains at

@@ -123,6 +123,7 @@ _SIGNATURES = {
     "mf_sparse_conv3d_k4s2_points_cl_fwd": ([_p, _i64, _p, _p, _i64, _f, _f, _f, _f, _p, _p, _p, _p, _p] + [_i] * 6 + [_p], _i),
     "mf_interpolate_voxel_grid_cl_fwd": ([_p, _p, _p, _i64, _i, _i, _i, _i, _i, _p, _i64, _p], _i),
     "mf_occupancy_convs_fwd": ([_p] * 7 + [_i] * 2 + [_p], _i),
+    "mf_occupancy_convs_split_fwd": ([_p] * 8 + [_i] * 2 + [_p], _i),
     "mf_linear_fwd": ([_p, _i64, _i, _p, _i64, _i, _p, _i64, _p, _i64] + [_i] * 7 + [_p], _i),
     "mf_cast_rows_bf16": ([_p, _i64, _p, _i64, _i64, _i, _p], _i),
     "mf_relu_mask_bf16": ([_p, _p, _p, _p, _i64, _p], _i),

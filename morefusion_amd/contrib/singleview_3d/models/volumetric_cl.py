@@ -15,11 +15,12 @@ per-point heads) for ``torch.no_grad()`` on the MI355X with every 3-D operator h
                      heads as ONE [n, 984] x [984, 1920] GEMM, layers 2-4 with the heads side by side, each
                      reading / writing its column block (under bf16 autocast: stock ``F.linear``)
 
-From ``SPLIT_MIN_BATCH`` objects on (fp32 inference, ``split_bf16``), conv4 and the heads' first layer run as
-split-bf16 GEMMs on the bf16 MFMA instead (mf_conv3d_k4s2_split_fwd / mf_linear_split_fwd): sparse
-conv3's reduce writes the split form of h3 beside the fp32 grid, the samplers write their columns of the heads'
-input straight into its split form Fs [n, 2 x 992] (hi columns, then lo columns), the point-MLP columns are split
-by one mf_split_bf16 call.
+From ``SPLIT_MIN_BATCH`` objects on (fp32 inference, ``split_bf16``), conv4, the heads' first layer and conv3's
+occupancy channels run as split-bf16 GEMMs on the bf16 MFMA instead (mf_conv3d_k4s2_split_fwd /
+mf_linear_split_fwd): sparse conv3's reduce writes the split form of h3 beside the fp32 grid, the samplers write their
+columns of the heads' input straight into its split form Fs [n, 2 x 992] (hi columns, then lo columns), the point-MLP
+columns are split by one mf_split_bf16 call, and -- from ``pose``, the inference path -- the second occupancy convolution
+writes its 16 channels in split form only (mf_occupancy_convs_split_fwd).
 
 Grids are [B, D^3, C] (a voxel's channels are contiguous: the implicit GEMM's K runs over
 (tap, channel) without gathers, and a trilinear corner is one coalesced row read); nothing is
@@ -42,13 +43,14 @@ F_COLS, F_LD = 984, 992
 # Smallest batch (objects) from which a layer takes the split-bf16 path; below it the fp32-MFMA kernels run as before
 # (tools/time_volumetric_split.py, profiles/volumetric_split_bf16_layers.csv: at one object conv4 has 4 output tiles of
 # 256 x 256 for 256 CUs).  Static, like backbone2d.SPLIT_MIN_BATCH.
-SPLIT_MIN_BATCH = {"conv4": 4, "heads1": 4}
+SPLIT_MIN_BATCH = {"conv4": 4, "heads1": 4, "conv3_occ": 4}
 
 
 class ChannelsLastVolumetric:
     """Weight packs, workspaces and the launch sequence; one instance per Model (and device)."""
 
     split_bf16 = True  # conv4 and heads layer 1 as split-bf16 GEMMs in fp32 inference (class switch: A/B without rebuild)
+    split_conv3_occ = True  # conv3's 16 occupancy channels too (a layer's own switch, under split_bf16: ``split_<layer>``)
 
     def __init__(self, model):
         self.m = model
@@ -123,8 +125,8 @@ class ChannelsLastVolumetric:
     # ---- the split-bf16 path ------------------------------------------------------
     def _split_path(self, layer, B):
         """fp32 inference on the MFMA path with at least SPLIT_MIN_BATCH[layer] objects."""
-        return (self.split_bf16 and self.mfma_linear and not torch.is_autocast_enabled()
-                and not torch.is_grad_enabled() and B >= SPLIT_MIN_BATCH[layer])
+        return (self.split_bf16 and getattr(self, "split_" + layer, True) and self.mfma_linear
+                and not torch.is_autocast_enabled() and not torch.is_grad_enabled() and B >= SPLIT_MIN_BATCH[layer])
 
     def conv_k4s2_split(self, name, conv, xs_cl, B, D, cin, c_off=0, relu=True, bias=True, out_split=None):
         """xs_cl bf16 [B, D^3, 2 cin] (hi | lo) -> fp32 [B, (D/2)^3, Cout] through the split-bf16 implicit GEMM
@@ -181,12 +183,19 @@ class ChannelsLastVolumetric:
                                          h1.stride(0), None, 0, 0, ws.data_ptr(), nbytes, n, N, F_LD,
                                          _lib.stream_ptr()), "mf_linear_split_fwd")
 
-    def occupancy(self, grid):
-        """grid_nontarget_empty [B, D, D, D] -> relu(conv2_occ(relu(conv1_occ))) as [B, D^3, 16]."""
+    def occupancy(self, grid, split=False):
+        """grid_nontarget_empty [B, D, D, D] -> relu(conv2_occ(relu(conv1_occ))) as [B, D^3, 16]; ``split``: in split
+        form instead, bf16 [B, D^3, 2 x 16] (hi | lo of the same fp32 values, written by the convolution's own launch)."""
         B, D = grid.shape[0], grid.shape[1]
         g = _lib.f32c(grid)
         w1, b1, w2, b2 = self._occ_pack()
         h1 = self._scratch("occ_h1", (B, D ** 3, 8), g.device)
+        if split:
+            h2s = self._scratch("occ_h2_split", (B, D ** 3, 32), g.device, torch.bfloat16)
+            _lib.check(_lib.lib().mf_occupancy_convs_split_fwd(g.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+                                                               b2.data_ptr(), h1.data_ptr(), None, h2s.data_ptr(), B, D,
+                                                               _lib.stream_ptr()), "mf_occupancy_convs_split_fwd")
+            return h2s
         h2 = torch.empty((B, D ** 3, 16), dtype=torch.float32, device=g.device)
         _lib.check(_lib.lib().mf_occupancy_convs_fwd(g.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
                                                      b2.data_ptr(), h1.data_ptr(), h2.data_ptr(), B, D,
@@ -220,10 +229,14 @@ class ChannelsLastVolumetric:
             x_rows.data_ptr(), bi.data_ptr(), _lib.stream_ptr()), "mf_point_prep")
         return pts, tc4, x_rows, bi
 
-    def features(self, values, points_cam, pitch, origin, grid_nontarget_empty):
+    def features(self, values, points_cam, pitch, origin, grid_nontarget_empty, occ_split=False):
         """values [B,32,P] image features, points_cam [B,3,P] camera-frame coordinates, pitch [B], origin [B,3],
         no-entry grid [B,D,D,D] (or None) -> (F [B*P, 984] = feat1 | feat2 | feat3 | feat4 per point,
-        voxel-frame points [n,3])."""
+        voxel-frame points [n,3]).
+        ``occ_split``: conv3's occupancy channels may take the split-bf16 GEMM (``_split_path("conv3_occ", B)``
+        decides).  Off by default: as a stage of its own ``features`` returns the h3 of the fp32 kernels, bit for bit
+        whatever ``split_bf16`` says (its samples in F / Fs are compared that way); ``pose``, the inference path, asks
+        for it."""
         m = self.m
         B, _, P = points_cam.shape
         n, D = B * P, m._voxel_dim
@@ -255,7 +268,10 @@ class ChannelsLastVolumetric:
 
         # conv3 = dense 16 occupancy channels (implicit GEMM) + sparse 144 voxelized channels
         dense = None
-        if m._with_occupancy:
+        if m._with_occupancy and occ_split and self._split_path("conv3_occ", B):
+            h_occ = self.occupancy(grid_nontarget_empty, split=True)
+            dense = self.conv_k4s2_split("conv3_occ", m.conv3, h_occ, B, D, cin=16, c_off=144, relu=False, bias=False)
+        elif m._with_occupancy:
             h_occ = self.occupancy(grid_nontarget_empty)
             dense = self.conv_k4s2("conv3_occ", m.conv3, h_occ, B, D, cin=16, c_off=144, relu=False, bias=False)
         h3s = self._scratch("h3_split", (B, (D // 2) ** 3, 2 * m.conv3.out_channels), dev, torch.bfloat16) if split4 else None
@@ -380,7 +396,7 @@ class ChannelsLastVolumetric:
     def pose(self, class_id, values, points_cam, pitch, origin, grid_nontarget_empty):
         """The whole volumetric part: -> (rot [B,P,4], trans [B,P,3], conf [B,P]) of each object's class."""
         B, _, P = points_cam.shape
-        feat, pts = self.features(values, points_cam, pitch, origin, grid_nontarget_empty)
+        feat, pts = self.features(values, points_cam, pitch, origin, grid_nontarget_empty, occ_split=True)
         o, np4 = self.heads(feat, B, P, raw=True)
         if o is not None:
             dev = values.device

@@ -253,10 +253,13 @@ __global__ __launch_bounds__(256) void k_to_channels_last(const float *__restric
 // object: VALU work.  One lane per output voxel, all output channels in registers, channels-last
 // in / out (the 16-channel result feeds conv3's implicit GEMM as it is); the weights are uniform ->
 // scalar loads, every v_fma takes its weight from an SGPR.  Packed weights: w[tap][ci][co].
+// ``outs`` (optional; CO % 8 == 0): the split-bf16 form of the same fp32 values, [voxel][2 CO] bf16 = a voxel's CO hi
+// channels, then its CO lo channels (hi = bf16(v), lo = bf16(v - hi), round-to-nearest-even; v - hi is exact): the
+// operand of mf_conv3d_k4s2_split_fwd, written here as k_sc_reduce_cl writes its own.  ``out`` may then be null.
 template <int CI, int CO, int DIL>
 __global__ __launch_bounds__(256) void k_occ_conv3(const float *__restrict__ x, const float *__restrict__ w,
                                                    const float *__restrict__ bias, float *__restrict__ out,
-                                                   int B, int D) {
+                                                   uint16_t *__restrict__ outs, int B, int D) {
   const int64_t total = (int64_t)B * D * D * D;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
@@ -297,12 +300,33 @@ __global__ __launch_bounds__(256) void k_occ_conv3(const float *__restrict__ x, 
       }
     }
   }
-  float *dst = out + i * CO;
 #pragma unroll
-  for (int q = 0; q < CO / 4; ++q)
-    reinterpret_cast<float4 *>(dst)[q] =
-        make_float4(fmaxf(acc[4 * q], 0.0f), fmaxf(acc[4 * q + 1], 0.0f), fmaxf(acc[4 * q + 2], 0.0f),
-                    fmaxf(acc[4 * q + 3], 0.0f));
+  for (int co = 0; co < CO; ++co) acc[co] = fmaxf(acc[co], 0.0f);
+  if (out) {
+    float *dst = out + i * CO;
+#pragma unroll
+    for (int q = 0; q < CO / 4; ++q)
+      reinterpret_cast<float4 *>(dst)[q] = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+  }
+  if constexpr (CO % 8 == 0) {
+    if (outs) {
+      uint32_t h[CO], l[CO];
+#pragma unroll
+      for (int co = 0; co < CO; ++co) {
+        h[co] = mf::bf16_bits(acc[co]);
+        l[co] = mf::bf16_bits(acc[co] - mf::bf16_lo(h[co]));
+      }
+      uint16_t *dst = outs + i * (2 * CO);
+#pragma unroll
+      for (int q = 0; q < CO / 8; ++q) {
+        const int c = 8 * q;
+        *reinterpret_cast<uint4 *>(dst + c) =
+            make_uint4(h[c] | h[c + 1] << 16, h[c + 2] | h[c + 3] << 16, h[c + 4] | h[c + 5] << 16, h[c + 6] | h[c + 7] << 16);
+        *reinterpret_cast<uint4 *>(dst + CO + c) =
+            make_uint4(l[c] | l[c + 1] << 16, l[c + 2] | l[c + 3] << 16, l[c + 4] | l[c + 5] << 16, l[c + 6] | l[c + 7] << 16);
+      }
+    }
+  }
 }
 
 int ilog2(int x) {
@@ -378,18 +402,43 @@ extern "C" int mf_to_channels_last(const float *src, float *dst, int32_t B, int3
 
 /* w1 [27][1][8], w2 [27][8][16] (tap-major, output channel innermost), biases [8], [16];
  * grid [B,D,D,D] -> h1 [B,D^3,8] (scratch) -> h2 [B,D^3,16], both ReLU-ed, channels-last. */
-extern "C" int mf_occupancy_convs_fwd(const float *grid, const float *w1, const float *b1, const float *w2,
-                                      const float *b2, float *h1, float *h2, int32_t B, int32_t D,
-                                      mfStream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+namespace {
+int occupancy_convs(const float *grid, const float *w1, const float *b1, const float *w2, const float *b2, float *h1,
+                    float *h2, void *h2s, int32_t B, int32_t D, hipStream_t stream, const char *what) {
   if (B <= 0) return 0;
   const int64_t total = (int64_t)B * D * D * D;
-  if (total * 16 >= (1ll << 31)) {
-    mf::set_last_error(hipErrorInvalidValue, "occupancy_convs: B * D^3 * 16 must stay below 2^31");
+  if (total * 16 >= (1ll << 31) || (!h2 && !h2s) || ((uintptr_t)h2s & 15)) {
+    mf::set_last_error(hipErrorInvalidValue,
+                       "occupancy_convs: B * D^3 * 16 must stay below 2^31; an output (the split one 16-byte aligned)");
     return -(int)hipErrorInvalidValue;
   }
   const unsigned nb = (unsigned)((total + 255) / 256);
-  hipLaunchKernelGGL((k_occ_conv3<1, 8, 1>), dim3(nb), dim3(256), 0, stream, grid, w1, b1, h1, B, D);
-  hipLaunchKernelGGL((k_occ_conv3<8, 16, 2>), dim3(nb), dim3(256), 0, stream, (const float *)h1, w2, b2, h2, B, D);
-  return mf::check_launch("mf_occupancy_convs_fwd");
+  hipLaunchKernelGGL((k_occ_conv3<1, 8, 1>), dim3(nb), dim3(256), 0, stream, grid, w1, b1, h1, (uint16_t *)nullptr, B, D);
+  hipLaunchKernelGGL((k_occ_conv3<8, 16, 2>), dim3(nb), dim3(256), 0, stream, (const float *)h1, w2, b2, h2,
+                     (uint16_t *)h2s, B, D);
+  return mf::check_launch(what);
+}
+}  // namespace
+
+extern "C" int mf_occupancy_convs_fwd(const float *grid, const float *w1, const float *b1, const float *w2,
+                                      const float *b2, float *h1, float *h2, int32_t B, int32_t D,
+                                      mfStream_t stream_) {
+  if (B > 0 && !h2) {
+    mf::set_last_error(hipErrorInvalidValue, "occupancy_convs: h2 is null");
+    return -(int)hipErrorInvalidValue;
+  }
+  return occupancy_convs(grid, w1, b1, w2, b2, h1, h2, nullptr, B, D, (hipStream_t)stream_, "mf_occupancy_convs_fwd");
+}
+
+/* mf_occupancy_convs_fwd with the split-bf16 form of h2 written by the same launch: h2s bf16 [B, D^3, 2 x 16] (a
+ * voxel's 16 hi channels, then its 16 lo channels), the split of the fp32 value h2 holds; h2 may be null (then only
+ * the split form is written), h2s must not. */
+extern "C" int mf_occupancy_convs_split_fwd(const float *grid, const float *w1, const float *b1, const float *w2,
+                                            const float *b2, float *h1, float *h2, void *h2s, int32_t B, int32_t D,
+                                            mfStream_t stream_) {
+  if (B > 0 && !h2s) {
+    mf::set_last_error(hipErrorInvalidValue, "occupancy_convs_split: h2s is null");
+    return -(int)hipErrorInvalidValue;
+  }
+  return occupancy_convs(grid, w1, b1, w2, b2, h1, h2, h2s, B, D, (hipStream_t)stream_, "mf_occupancy_convs_split_fwd");
 }

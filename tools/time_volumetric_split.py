@@ -1,8 +1,11 @@
 """Per-layer time of the volumetric part's layers on the fp32-MFMA kernels vs the split-bf16 GEMMs (epilogue and split-K
 finish pass included), at --batches objects, and the volumetric part / Model.predict with the split path on / off.
 CUDA-event medians over --reps launches after a warm-up.  -> CSV on stdout (profiles/volumetric_split_bf16_layers.csv,
-DESIGN.md 8.4: the basis of volumetric_cl.SPLIT_MIN_BATCH)."""
+DESIGN.md 8.4: the basis of volumetric_cl.SPLIT_MIN_BATCH).
+--conv3-occ: conv3's 16 occupancy channels instead -- the layer (split-K finish included) and the occupancy branch that
+feeds it in both forms, and the layer under the other plans the knobs allow (profiles/volumetric_split2_layers.csv)."""
 import argparse
+import os
 import statistics
 
 import torch
@@ -35,17 +38,50 @@ def split(x):
     return torch.cat([hi, (x - hi.float()).to(torch.bfloat16)], dim=-1).contiguous()
 
 
+def conv3_occ(model, vol, L, args):
+    """B,what,fp32_ms,split_ms,tile,S,gflop,split_tflops_fp32_equivalent; ``what`` = conv3_occ (the default plan),
+    conv3_occ@<knobs> (the same layer under a forced plan), occupancy_convs (the producer: fp32 store / split store)."""
+    plans = [("", {}), ("@tile256_S1", {"MF_NT_BIG": "2", "MF_NT_SPLITK": "1"}),
+             ("@tile256_S3", {"MF_NT_BIG": "2", "MF_NT_SPLITK": "3"}), ("@tile128", {"MF_NT_BIG": "0"})]
+    print("B,what,fp32_ms,split_ms,tile,S,gflop,split_tflops_fp32_equivalent")
+    for B in [int(b) for b in args.batches.split(",")]:
+        grid = (torch.rand(B, 32, 32, 32, device="cuda") < 0.4).float()
+        t32 = timed(lambda: vol.occupancy(grid), args.reps)
+        ts = timed(lambda: vol.occupancy(grid, split=True), args.reps)
+        print(f"{B},occupancy_convs,{t32:.4f},{ts:.4f},,,,", flush=True)
+        h = vol.occupancy(grid).clone()
+        hs = vol.occupancy(grid, split=True)
+        kw = dict(cin=16, c_off=144, relu=False, bias=False)
+        t32 = timed(lambda: vol.conv_k4s2("conv3_occ", model.conv3, h, B, 32, **kw), args.reps)
+        g = 2.0 * B * 16 ** 3 * 256 * 64 * 16 / 1e9
+        for tag, env in plans:
+            os.environ.update(env)
+            try:
+                ts = timed(lambda: vol.conv_k4s2_split("conv3_occ", model.conv3, hs, B, 32, **kw), args.reps)
+                tile = L.mf_gemm_bf16_last_tile()
+                S = L.mf_conv3d_k4s2_split_workspace_bytes(B, 16, 256, 32) // (B * 16 ** 3 * 256 * 4) or 1
+            finally:
+                for k in env:
+                    del os.environ[k]
+            print(f"{B},conv3_occ{tag},{t32:.4f},{ts:.4f},{tile},{S},{g:.2f},{g / ts:.1f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--batches", default="1,2,4,8")
     ap.add_argument("--no-predict", action="store_true")
+    ap.add_argument("--conv3-occ", action="store_true")
     args = ap.parse_args()
     torch.backends.cudnn.benchmark = False
     torch.manual_seed(0)
     model = Model(n_fg_class=21, with_occupancy=True).cuda().eval()
     vol = ChannelsLastVolumetric(model)
     L = _lib.lib()
+    if args.conv3_occ:
+        with torch.no_grad():
+            conv3_occ(model, vol, L, args)
+        return
     print("B,what,fp32_ms,split_ms,gflop,split_tflops_fp32_equivalent")
     with torch.no_grad():
         for B in [int(b) for b in args.batches.split(",")]:
