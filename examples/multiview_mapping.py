@@ -3,7 +3,10 @@ shuffled in every frame -> InstanceTracker (render the maps, match the detection
 integrate_tracked_frame (one occupancy map per stable id) -> target grids -> Model.predict -> ObjectMapping (an
 object is spawned once three of its poses agree).  Prints the id table of every frame.
 
-    python examples/multiview_mapping.py [--frames 3] [--model <chainer .npz checkpoint>]
+    python examples/multiview_mapping.py [--frames 3] [--model <chainer .npz checkpoint>] [--track-camera]
+
+--track-camera: the sensor pose is CameraTracker.track(depth) (dense depth alignment, frame to frame, anchored at frame
+0's pose) instead of the sequence's ground truth; its error against the ground truth is printed per frame.
 """
 import argparse
 import os
@@ -22,10 +25,22 @@ from morefusion_amd.contrib.singleview_3d.models.model import PitchTableModels  
 THRESHOLDS = dict(min_mask=20, min_bbox=30, min_side=24)
 
 
+def track_camera(camera, depth, T_true, k):
+    """CameraTracker's pose of the frame, and its error against the ground truth on stdout."""
+    T = camera.track(depth).cpu().numpy()
+    D = np.linalg.inv(T_true) @ T
+    angle = np.degrees(np.arccos(np.clip((np.trace(D[:3, :3]) - 1) / 2, -1, 1)))
+    state = "" if k == 0 else (" LOST" if camera.lost else f" ({int(camera.stats[-1, 0])} pairs)")
+    print(f"frame {k}: tracked camera off by {np.linalg.norm(T[:3, 3] - T_true[:3, 3]) * 1e3:.3f} mm, "
+          f"{angle:.4f} deg{state}")
+    return T
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=3)
     ap.add_argument("--model", help="chainer .npz checkpoint of the reference")
+    ap.add_argument("--track-camera", action="store_true", help="estimate the sensor pose from the depth images")
     args = ap.parse_args()
     frames = morefusion.synthetic.make_tracking_sequence(0, args.frames)
     models = PitchTableModels()
@@ -48,8 +63,14 @@ def main():
     tracker = morefusion.contrib.InstanceTracker(mapping, thresholds=THRESHOLDS)
     voter = morefusion.contrib.ObjectMapping(points_of, lambda c: c in morefusion.synthetic.CLASS_IDS_SYMMETRIC)
     ids_of_object = {}
+    camera = None
+    if args.track_camera:
+        height, width = frames[0]["depth"].shape
+        camera = morefusion.contrib.CameraTracker(frames[0]["K"], height, width, T_first=frames[0]["T_sensor_to_map"])
     for k, f in enumerate(frames):
         K, T = f["K"], f["T_sensor_to_map"]
+        if camera is not None:
+            T = track_camera(camera, to_gpu(f["depth"]), T, k)
         pcd = morefusion.geometry.pointcloud_from_depth(f["depth"], K[0, 0], K[1, 1], K[0, 2], K[1, 2])
         tracked, merged, class_of, _ = tracker.track(to_gpu(pcd.astype(np.float32)), to_gpu(f["label_detected"]),
                                                      f["class_ids_by_detection"], K, T)

@@ -7,10 +7,14 @@ grid_target / grid_noentry, as collision_based_pose_refinement.py passes them.  
 before and after the refinement.
 
     python examples/online_pose_refinement.py [--frames 3] [--model <chainer .npz checkpoint>] [--render-service]
+                                              [--track-camera]
 
 --render-service: the tracker matches against the reference's render-service route (use_render_service,
 OctomapServer.cpp:126-135) -- OctomapServer.grids_in_map_frame meshed and rasterised (contrib.render_voxel_grids) --
 instead of the per-pixel ray-cast.
+--track-camera: the sensor pose handed to the tracker and the server is CameraTracker.track(depth) (dense depth
+alignment, frame to frame, anchored at frame 0's pose) instead of the sequence's ground truth; its error against the
+ground truth is printed per frame.
 """
 import argparse
 import os
@@ -30,11 +34,23 @@ THRESHOLDS = dict(min_mask=20, min_bbox=30, min_side=24)
 TO_GROUND = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0.2], [0, 0, 0, 1]], np.float64)
 
 
+def track_camera(camera, depth, T_true, k):
+    """CameraTracker's pose of the frame, and its error against the ground truth on stdout."""
+    T = camera.track(depth).cpu().numpy()
+    D = np.linalg.inv(T_true) @ T
+    angle = np.degrees(np.arccos(np.clip((np.trace(D[:3, :3]) - 1) / 2, -1, 1)))
+    state = "" if k == 0 else (" LOST" if camera.lost else f" ({int(camera.stats[-1, 0])} pairs)")
+    print(f"frame {k}: tracked camera off by {np.linalg.norm(T[:3, 3] - T_true[:3, 3]) * 1e3:.3f} mm, "
+          f"{angle:.4f} deg{state}")
+    return T
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=3)
     ap.add_argument("--model", help="chainer .npz checkpoint of the reference")
     ap.add_argument("--render-service", action="store_true", help="render the maps as meshes (render_voxel_grids.py)")
+    ap.add_argument("--track-camera", action="store_true", help="estimate the sensor pose from the depth images")
     args = ap.parse_args()
     frames = morefusion.synthetic.make_tracking_sequence(0, args.frames)
     models = PitchTableModels()
@@ -59,8 +75,15 @@ def main():
         tracker = morefusion.contrib.InstanceTracker(server.mapping, thresholds=THRESHOLDS, render="mesh", server=server)
     else:
         tracker = morefusion.contrib.InstanceTracker(server.mapping, thresholds=THRESHOLDS)
+    camera = None
+    if args.track_camera:
+        height, width = frames[0]["depth"].shape
+        camera = morefusion.contrib.CameraTracker(frames[0]["K"], height, width,
+                                                  T_first=TO_GROUND @ frames[0]["T_sensor_to_map"])
     for k, f in enumerate(frames):
         K, T = f["K"], TO_GROUND @ f["T_sensor_to_map"]
+        if camera is not None:
+            T = track_camera(camera, to_gpu(f["depth"]), T, k)
         pcd = morefusion.geometry.pointcloud_from_depth(f["depth"], K[0, 0], K[1, 1], K[0, 2], K[1, 2])
         tracked, _, class_of, _ = tracker.track(to_gpu(pcd.astype(np.float32)), to_gpu(f["label_detected"]),
                                                 f["class_ids_by_detection"], K, T,

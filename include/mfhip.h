@@ -1315,6 +1315,76 @@ int mf_occserver_map_grids(const mfOccTree *trees, int32_t n_trees, const int32_
                            const float *center_map, int32_t B, int32_t D, double *origin, float *grid,
                            mfStream_t stream);
 
+/* ---- camera tracking: dense point-to-plane depth alignment (contrib/camera_tracking.py, csrc/camtrack.hip) ----
+ * The tracking step of KinectFusion: projective data association and point-to-plane Gauss-Newton over a depth
+ * pyramid, B independent alignments per call, float64 throughout (DESIGN.md "Camera tracking"; tests/camtrack_ref.py
+ * is the NumPy mirror, bit for bit).  All arrays are DEVICE arrays unless said otherwise; every call is asynchronous
+ * on `stream`, allocates nothing and never synchronises.  Refusals return < 0.
+ *
+ * Level l of a pyramid has H_l = height >> l rows and W_l = width >> l columns (an odd size drops its last row or
+ * column) and the intrinsics fx_(l+1) = fx_l / 2, fy_(l+1) = fy_l / 2, cx_(l+1) = (cx_l - 0.5) / 2, cy_(l+1) =
+ * (cy_l - 0.5) / 2.  A PYRAMID is one buffer of mf_camtrack_workspace_bytes(.., MF_CAMTRACK_PYRAMID) bytes: for
+ * l = 0 .. levels - 1 in turn the parts depth_l float32 [B, H_l, W_l], vertex_l float64 [B, H_l, W_l, 3], normal_l
+ * float64 [B, H_l, W_l, 3], then rect int32 [levels, B, 4] = (0, 0, H_l, W_l); every part starts at the next
+ * multiple of 16 bytes.
+ *   depth_0 = the input.  A sample is valid iff it is > 0 (NaN is not).  depth_(l+1)(y, x): of the samples (2y, 2x),
+ *   (2y, 2x + 1), (2y + 1, 2x), (2y + 1, 2x + 1) of depth_l, in this order, those that are valid and have
+ *   double(d) - double(d_min) <= block_band (d_min the smallest valid one) are summed in float64 in this order,
+ *   divided by their number and rounded to float32; NaN if none is valid.
+ *   vertex_l(r, c) = ((z (c - cx_l)) / fx_l, (z (r - cy_l)) / fy_l, z) with z = double(depth), NaN x 3 if invalid.
+ *   normal_l = mf_pick_normals of vertex_l with the rectangle (0, 0, H_l, W_l) (that entry point is called). */
+#define MF_CAMTRACK_MAX_LEVELS 8
+#define MF_CAMTRACK_MAX_BATCH 1024
+#define MF_CAMTRACK_MAX_PIXELS (1LL << 26) /* B * height * width */
+#define MF_CAMTRACK_MAX_ITERATIONS 4096    /* summed over the levels */
+#define MF_CAMTRACK_PYRAMID 0
+#define MF_CAMTRACK_ALIGN 1
+#define MF_CAMTRACK_GROUP_PIXELS 1024 /* pixels of one workgroup of the residual launch: 256 lanes x 4 */
+#define MF_CAMTRACK_PARTIAL 32        /* doubles of one workgroup's partial (29 used) */
+#define MF_CAMTRACK_TRACKING 0
+#define MF_CAMTRACK_LOST_PAIRS 1 /* fewer than min_pairs pairs */
+#define MF_CAMTRACK_LOST_PIVOT 2 /* a Cholesky pivot was not > 0 */
+/* Host-only: bytes of a pyramid (which = MF_CAMTRACK_PYRAMID) or of mf_camtrack_align's workspace (which =
+ * MF_CAMTRACK_ALIGN) for B images of height x width and `levels` levels; < 0 unless 1 <= B <= MF_CAMTRACK_MAX_BATCH,
+ * height, width <= MF_RENDER_MAX_SIDE, B height width <= MF_CAMTRACK_MAX_PIXELS, 1 <= levels <=
+ * MF_CAMTRACK_MAX_LEVELS and the coarsest level is at least 8 x 8. */
+int64_t mf_camtrack_workspace_bytes(int32_t B, int32_t height, int32_t width, int32_t levels, int32_t which);
+/* depth float32 [B, height, width] -> pyramid (every part written).  fx, fy != 0, block_band >= 0. */
+int mf_camtrack_prepare(const float *depth, int32_t B, int32_t height, int32_t width, int32_t levels, double fx,
+                        double fy, double cx, double cy, double block_band, void *pyramid, mfStream_t stream);
+/* Align the pyramid `current` to the pyramid `reference` (both of B, height, width, levels and fx .. cy).
+ * T_ref_to_map, T_init float64 [B, 4, 4] row-major (rigid; T_init = the first guess of T_cur_to_map); `iterations`
+ * is a HOST array int32 [levels], the Gauss-Newton iterations at the coarsest level first, each >= 0, n_iters their
+ * sum.  Outputs: pose float64 [B, 7] = unit quaternion (w, x, y, z) then translation, T_cur_to_map float64 [B, 4, 4]
+ * = the matrix of `pose`, status int32 [B] (MF_CAMTRACK_TRACKING / _LOST_*), stats float64 [B, n_iters, 3] = (pairs,
+ * sum r^2, |increment|) of each iteration (zeros: the alignment was lost before it).
+ *
+ * Start (one launch): q = the quaternion of T_init's rotation (Shepperd's four branches, normalised), t its
+ * translation; the rigid inverse of T_ref_to_map.  Then per iteration TWO launches:
+ *   residuals -- a workgroup of 256 lanes per MF_CAMTRACK_GROUP_PIXELS pixels and alignment; lane t takes the
+ *   pixels p = 1024 g + 256 s + t, s = 0 .. 3 in turn (p row-major over the level).  A pixel with a valid vertex v
+ *   and normal n: v_g = R v + t, n_g = R n, p_r = T_ref^-1 v_g; rejected if p_r.z is not > 0; (col, row) =
+ *   floor((fx p_r.x) / p_r.z + cx + 0.5), floor((fy p_r.y) / p_r.z + cy + 0.5), rejected outside the image or where
+ *   the reference vertex or normal there has a NaN; v_ref_g = R_ref v_ref + t_ref, n_ref_g = R_ref n_ref, d =
+ *   v_ref_g - v_g; rejected if |d| > distance_threshold or n_g . n_ref_g < cos_angle_threshold.  r = n_ref_g . d,
+ *   J = (n_ref_g, v_g x n_ref_g).  Every 3-term sum is ((a + b) + c) (+ t).  A lane adds its pairs' 28 terms --
+ *   J_i J_j for i <= j row by row (21), J_i r (6), r r -- in the order s = 0 .. 3; the 64 lanes of a wave fold by
+ *   x[l] += x[l + h] for h = 32, 16, .. 1; the 4 waves add as ((w0 + w1) + w2) + w3; the pair count is an integer.
+ *   One partial of MF_CAMTRACK_PARTIAL doubles per workgroup (term 28 = the count).
+ *   solve -- a workgroup per alignment: sub-sum j = 0 .. 7 adds the partials g = j, j + 8, .. in turn, the total is
+ *   ((((((s0 + s1) + s2) + s3) + s4) + s5) + s6) + s7.  pairs < min_pairs -> lost.  Cholesky A = L L^T row by row
+ *   (each inner product subtracted term by term in increasing index; a pivot not > 0 -> lost), forward and back
+ *   substitution likewise: xi = (xi_t, xi_r).  dq = (1, xi_r / 2) normalised, t = R(dq) t + xi_t, q = dq q
+ *   normalised (Hamilton product, terms added left to right).  |increment| = sqrt of the squares of xi summed left to
+ *   right.
+ * A lost alignment gets its status, its pose back to the initial one and is left untouched by every later launch;
+ * the others go on.  Only + - x / sqrt and floor are used.  workspace: MF_CAMTRACK_ALIGN bytes. */
+int mf_camtrack_align(const void *current, const void *reference, int32_t B, int32_t height, int32_t width,
+                      int32_t levels, double fx, double fy, double cx, double cy, const double *T_ref_to_map,
+                      const double *T_init, const int32_t *iterations, double distance_threshold,
+                      double cos_angle_threshold, int32_t min_pairs, double *pose, double *T_cur_to_map,
+                      int32_t *status, double *stats, void *workspace, mfStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

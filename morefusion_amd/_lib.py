@@ -263,6 +263,9 @@ _SIGNATURES = {
     "mf_gridmesh_smooth": ([_p, _p, _p, _i64, _d, _d, _i, _p, _p], _i),
     "mf_gridmesh_label": ([_p, _p, _p, _i, _i, _p, _p], _i),
     "mf_occserver_map_grids": ([_p, _i, _p, _p, _p, _i, _i, _p, _p, _p], _i),
+    "mf_camtrack_workspace_bytes": ([_i] * 5, _i64),
+    "mf_camtrack_prepare": ([_p] + [_i] * 4 + [_d] * 5 + [_p, _p], _i),
+    "mf_camtrack_align": ([_p, _p] + [_i] * 4 + [_d] * 4 + [_p, _p, _p, _d, _d, _i] + [_p] * 6, _i),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -13,3 +13,4 @@ from .instance_tracking import InstanceTracker, render_instance_maps, render_vox
 from .object_mapping import ObjectMapping
 from .picking_order import SelectPickingOrder, get_picking_order, occlusion_analysis, quaternion_from_two_vectors
 from .octomap_server import OctomapServer
+from .camera_tracking import CameraTracker, align_depth
