@@ -7,7 +7,7 @@ grid_target / grid_noentry, as collision_based_pose_refinement.py passes them.  
 before and after the refinement.
 
     python examples/online_pose_refinement.py [--frames 3] [--model <chainer .npz checkpoint>] [--render-service]
-                                              [--track-camera]
+                                              [--track-camera | --track-model]
 
 --render-service: the tracker matches against the reference's render-service route (use_render_service,
 OctomapServer.cpp:126-135) -- OctomapServer.grids_in_map_frame meshed and rasterised (contrib.render_voxel_grids) --
@@ -15,6 +15,8 @@ instead of the per-pixel ray-cast.
 --track-camera: the sensor pose handed to the tracker and the server is CameraTracker.track(depth) (dense depth
 alignment, frame to frame, anchored at frame 0's pose) instead of the sequence's ground truth; its error against the
 ground truth is printed per frame.
+--track-model: the same through ModelTracker: every frame is aligned to a ray-cast of the TSDF volume that the earlier
+frames were fused into (1 cm voxels over the scene), frame to model instead of frame to frame.
 """
 import argparse
 import os
@@ -30,12 +32,14 @@ from morefusion_amd.contrib.singleview_3d.models.model import PitchTableModels  
 
 # the synthetic objects are 30 .. 100 pixels across: the reference's vetoes (40 / 80 / 60) scaled to them
 THRESHOLDS = dict(min_mask=20, min_bbox=30, min_side=24)
+# --track-model: a 1 cm volume over the synthetic scene (x -0.8 .. 0.8, y -0.62 .. 0.3, z 0.3 .. 1.5) in the ground frame
+MODEL_VOLUME = dict(dims=(161, 121, 93), pitch=0.01, origin=(-0.8, 0.3, -0.1))
 # the synthetic scene has its table top at y = 0.2 with y pointing down: the server's map frame has it at z = 0, z up
 TO_GROUND = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0.2], [0, 0, 0, 1]], np.float64)
 
 
 def track_camera(camera, depth, T_true, k):
-    """CameraTracker's pose of the frame, and its error against the ground truth on stdout."""
+    """CameraTracker's (or ModelTracker's) pose of the frame, and its error against the ground truth on stdout."""
     T = camera.track(depth).cpu().numpy()
     D = np.linalg.inv(T_true) @ T
     angle = np.degrees(np.arccos(np.clip((np.trace(D[:3, :3]) - 1) / 2, -1, 1)))
@@ -51,7 +55,11 @@ def main():
     ap.add_argument("--model", help="chainer .npz checkpoint of the reference")
     ap.add_argument("--render-service", action="store_true", help="render the maps as meshes (render_voxel_grids.py)")
     ap.add_argument("--track-camera", action="store_true", help="estimate the sensor pose from the depth images")
+    ap.add_argument("--track-model", action="store_true",
+                    help="estimate the sensor pose by aligning every frame to the fused TSDF model")
     args = ap.parse_args()
+    if args.track_camera and args.track_model:
+        ap.error("--track-camera or --track-model, not both")
     frames = morefusion.synthetic.make_tracking_sequence(0, args.frames)
     models = PitchTableModels()
     pitch_of = lambda c: models.get_voxel_pitch(32, int(c))  # noqa: E731
@@ -80,6 +88,11 @@ def main():
         height, width = frames[0]["depth"].shape
         camera = morefusion.contrib.CameraTracker(frames[0]["K"], height, width,
                                                   T_first=TO_GROUND @ frames[0]["T_sensor_to_map"])
+    if args.track_model:
+        height, width = frames[0]["depth"].shape
+        camera = morefusion.contrib.ModelTracker(frames[0]["K"], height, width,
+                                                 morefusion.contrib.TsdfVolume(**MODEL_VOLUME),
+                                                 T_first=TO_GROUND @ frames[0]["T_sensor_to_map"])
     for k, f in enumerate(frames):
         K, T = f["K"], TO_GROUND @ f["T_sensor_to_map"]
         if camera is not None:

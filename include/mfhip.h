@@ -1385,6 +1385,73 @@ int mf_camtrack_align(const void *current, const void *reference, int32_t B, int
                       double cos_angle_threshold, int32_t min_pairs, double *pose, double *T_cur_to_map,
                       int32_t *status, double *stats, void *workspace, mfStream_t stream);
 
+/* ---- TSDF fusion: integrate depth frames into a volume, ray-cast it (contrib/tsdf_volume.py, csrc/tsdf.hip) ----
+ * The mapping half of KinectFusion: the model that frame-to-model tracking aligns to (DESIGN.md "TSDF fusion";
+ * tests/tsdf_ref.py is the NumPy mirror, bit for bit, written from this text).  All arrays are DEVICE arrays; every
+ * call is asynchronous on `stream`, allocates nothing and never synchronises.
+ *
+ * VOLUME: float32 [nz][ny][nx][2], x fastest, the pair (tsdf, weight) of voxel (i, j, k) at float index
+ * 2 ((k ny + j) nx + i).  The centre of voxel (i, j, k) is c_a = origin_a + pitch * double(index_a) in the MAP frame
+ * (origin_a, pitch float64; a = x, y, z with index i, j, k).  A fresh volume is (1, 0) everywhere; the caller fills it.
+ * POSE: T_sensor_to_map float64 [16] row-major ON THE DEVICE (R_ab = T[4 a + b], t_a = T[4 a + 3]); only these 12
+ * words are read.  Pinhole fx, fy, cx, cy; images [H][W] row-major.
+ * ARITHMETIC: float64, + - * / and floor only, nothing contracted, every expression associated as written here;
+ * float32 inputs are widened first, results are rounded to float32 at the store.  Every test is written so that a
+ * NaN fails it.
+ * Refused with -hipErrorInvalidValue (the function's name in mf_last_error_string) unless: nx, ny, nz >= 2 and
+ * nx ny nz < 2^31; pitch > 0; truncation > 0; max_weight >= 1; 1 <= H, W <= MF_RENDER_MAX_SIDE; fx, fy > 0;
+ * step > 0; 0 <= min_depth < max_depth; 1 <= max_steps <= MF_TSDF_MAX_STEPS; the arrays non-null (skip_flag and
+ * code_out may be null). */
+#define MF_TSDF_MAX_STEPS 65536
+#define MF_TSDF_RAY_HIT 0      /* depth_out = the zero crossing */
+#define MF_TSDF_RAY_LEFT 1     /* the samples ran past the far end of the box: no crossing */
+#define MF_TSDF_RAY_BACKFACE 2 /* the first sample with tsdf <= 0 had no valid positive sample right before it */
+#define MF_TSDF_RAY_MISS 3     /* the ray does not meet the box within [min_depth, max_depth] */
+#define MF_TSDF_RAY_CAP 4      /* max_steps samples taken without an end */
+/* Fuse one depth image into the volume.  One lane per voxel (256-lane workgroups over the flat voxel index).  If
+ * skip_flag is non-null and *skip_flag != 0 (an int32 on the device, e.g. the status of mf_camtrack_align) no lane
+ * does anything.  Per voxel, with c its centre:
+ *   e_a = c_a - t_a;  p_a = (R_0a e_0 + R_1a e_1) + R_2a e_2   (p = R^T (c - t), the camera frame; x, y, z = p)
+ *   required: z > 0
+ *   u = fx * (x / z) + cx,  v = fy * (y / z) + cy,  col = floor(u + 0.5),  row = floor(v + 0.5)
+ *   required: col >= 0, col <= W - 1, row >= 0, row <= H - 1 (compared as float64)
+ *   D = double(depth[row][col]);  required: D > 0
+ *   sdf = D - z;  required: sdf >= -truncation
+ *   f = sdf / truncation;  if f > 1 then f = 1
+ *   with (F_old, W_old) the voxel's pair: tsdf = float32((F_old * W_old + f) / (W_old + 1)),
+ *   w = W_old + 1, if w > max_weight then w = max_weight, weight = float32(w).
+ * A voxel that fails a requirement is not written. */
+int mf_tsdf_integrate(float *volume, int32_t nx, int32_t ny, int32_t nz, double origin_x, double origin_y,
+                      double origin_z, double pitch, double truncation, double max_weight, const float *depth,
+                      int32_t H, int32_t W, double fx, double fy, double cx, double cy,
+                      const double *T_sensor_to_map, const int32_t *skip_flag, mfStream_t stream);
+/* Ray-cast the volume into a depth image.  One lane per pixel (16 x 16 pixel workgroups); depth_out float32 [H][W]
+ * and code_out uint8 [H][W] (may be null) are written for EVERY pixel: depth_out = 0 unless the ray ends in a hit.
+ * Pixel (row, col):
+ *   q = ((col - cx) / fx, (row - cy) / fy);  d_a = (R_a0 q_0 + R_a1 q_1) + R_a2;  o_a = t_a
+ *   (the camera-frame ray is (q_0, q_1, 1): the ray parameter is the camera-frame depth)
+ *   lo_a = origin_a,  hi_a = origin_a + pitch * double(n_a - 1);  enter = min_depth,  exit = max_depth
+ *   for a = x, y, z in turn:
+ *     if d_a < 0 or d_a > 0:  t1 = (lo_a - o_a) / d_a,  t2 = (hi_a - o_a) / d_a,
+ *                             (tn, tf) = (t1, t2) if t1 < t2 else (t2, t1),
+ *                             enter = enter if tn <= enter else tn,  exit = exit if tf >= exit else tf
+ *     else unless d_a == 0 and o_a >= lo_a and o_a <= hi_a: MISS
+ *   unless enter <= exit: MISS
+ *   for k = 0, 1, ..:
+ *     s = enter + double(k) * step;  unless s <= exit: LEFT;  then if k >= max_steps: CAP
+ *     g_a = ((o_a + s * d_a) - origin_a) / pitch,  b_a = floor(g_a),  r_a = g_a - b_a
+ *     the sample is VALID iff b_a >= 0 and b_a <= n_a - 2 for all a (compared as float64) and the weights of the
+ *     eight voxels (b_x + {0, 1}, b_y + {0, 1}, b_z + {0, 1}) are all > 0.  Its value, from their tsdf V_xyz:
+ *       along x:  V_yz = V_0yz + r_x * (V_1yz - V_0yz);  along y:  V_z = V_0z + r_y * (V_1z - V_0z);
+ *       F = V_0 + r_z * (V_1 - V_0)
+ *     invalid: previous = none.  valid and F <= 0: if previous is a value P > 0 then HIT with
+ *       depth_out = float32((enter + double(k - 1) * step) + step * (P / (P - F)))
+ *     else BACKFACE.  valid otherwise: previous = F. */
+int mf_tsdf_raycast(const float *volume, int32_t nx, int32_t ny, int32_t nz, double origin_x, double origin_y,
+                    double origin_z, double pitch, double step, double min_depth, double max_depth,
+                    int32_t max_steps, int32_t H, int32_t W, double fx, double fy, double cx, double cy,
+                    const double *T_sensor_to_map, float *depth_out, uint8_t *code_out, mfStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,3 +14,4 @@ from .object_mapping import ObjectMapping
 from .picking_order import SelectPickingOrder, get_picking_order, occlusion_analysis, quaternion_from_two_vectors
 from .octomap_server import OctomapServer
 from .camera_tracking import CameraTracker, align_depth
+from .tsdf_volume import ModelTracker, TsdfVolume

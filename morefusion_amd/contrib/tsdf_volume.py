@@ -1,0 +1,189 @@
+"""TSDF fusion: depth frames integrated into a truncated-signed-distance volume, the volume ray-cast into a depth
+image, and a camera tracker that aligns every frame to that model (csrc/tsdf.hip, include/mfhip.h ``mf_tsdf_*``,
+DESIGN.md "TSDF fusion").
+
+``CameraTracker`` aligns a depth image to a reference depth image; against the previous frame every error is inherited,
+against the first frame tracking ends when the view has moved on.  The mapping half of KinectFusion (Newcombe et al.,
+ISMAR 2011) removes both: ``TsdfVolume.integrate`` fuses each frame into a volume of (tsdf, weight) pairs at its
+estimated pose, ``TsdfVolume.raycast`` renders the fused surface from any pose with sub-voxel depth, and
+``ModelTracker`` hands that render to ``CameraTracker.set_reference`` before every alignment.
+
+* ``TsdfVolume``: the volume and its two kernels.
+* ``ModelTracker``: ray-cast, align, integrate per frame; no host synchronisation in the loop, and a lost alignment is
+  kept out of the model by the device status word, not by reading it back.
+"""
+import math
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .camera_tracking import CameraTracker, _depth_tensor, _intrinsics, _pose_tensor
+
+MAX_STEPS = 65536  # MF_TSDF_MAX_STEPS (include/mfhip.h)
+RAY_HIT, RAY_LEFT, RAY_BACKFACE, RAY_MISS, RAY_CAP = range(5)  # MF_TSDF_RAY_*
+
+
+def _camera(K):
+    fx, fy, cx, cy = _intrinsics(K)
+    if not (fx > 0 and fy > 0):
+        raise ValueError("K: fx and fy must be > 0")
+    return fx, fy, cx, cy
+
+
+class TsdfVolume:
+    """``dims`` = (nx, ny, nz) voxels of ``pitch`` metres; voxel (i, j, k) has its centre at ``origin + pitch *
+    (i, j, k)`` in the map frame.  ``truncation`` (default ``4 * pitch``) is the distance at which the signed distance
+    saturates, ``max_weight`` the cap of the running average's weight.  The storage is one float32 tensor
+    ``[nz, ny, nx, 2]`` of (tsdf, weight) on ``device`` (default "cuda"; there is no CPU fallback), (1, 0) when fresh;
+    ``.tsdf`` and ``.weight`` are views of it."""
+
+    def __init__(self, dims, pitch, origin, truncation=None, max_weight=64.0, device=None):
+        dims = tuple(int(n) for n in dims)
+        if len(dims) != 3 or min(dims) < 2:
+            raise ValueError(f"dims = {dims}: three sizes (nx, ny, nz), each >= 2")
+        if dims[0] * dims[1] * dims[2] >= 1 << 31:
+            raise ValueError(f"dims = {dims}: fewer than 2^31 voxels")
+        self.dims, self.pitch = dims, float(pitch)
+        if not self.pitch > 0:
+            raise ValueError(f"pitch = {pitch}: must be > 0")
+        self.origin = tuple(_lib.as_float3(origin))
+        self.truncation = 4.0 * self.pitch if truncation is None else float(truncation)
+        if not self.truncation > 0:
+            raise ValueError(f"truncation = {truncation}: must be > 0")
+        self.max_weight = float(max_weight)
+        if not self.max_weight >= 1:
+            raise ValueError(f"max_weight = {max_weight}: must be >= 1")
+        self.device = torch.device("cuda" if device is None else device)
+        nx, ny, nz = dims
+        self.volume = torch.empty((nz, ny, nx, 2), dtype=torch.float32, device=self.device)
+        _lib.require_gpu(self.volume)
+        self.reset()
+
+    def reset(self):
+        self.volume[..., 0] = 1.0
+        self.volume[..., 1] = 0.0
+        return self
+
+    @property
+    def tsdf(self):
+        return self.volume[..., 0]
+
+    @property
+    def weight(self):
+        return self.volume[..., 1]
+
+    def _pose(self, T):
+        """NumPy [4, 4] -> a device copy; a device tensor is used in place (no copy if float64 and contiguous)."""
+        return _pose_tensor(T, 1, self.device, "T_sensor_to_map")
+
+    def max_steps(self, step):
+        """floor(the diagonal of the box of voxel centres / step) + 2."""
+        nx, ny, nz = self.dims
+        diagonal = self.pitch * math.sqrt(float((nx - 1) ** 2 + (ny - 1) ** 2 + (nz - 1) ** 2))
+        return int(math.floor(diagonal / step)) + 2
+
+    def integrate(self, depth, K, T_sensor_to_map, skip_if=None):
+        """Fuse ``depth`` (float [H, W] in metres, NumPy or tensor; NaN or <= 0: a hole) seen through the pinhole ``K``
+        from ``T_sensor_to_map`` ([4, 4]; a float64 device tensor is read in place by the kernel, e.g. the pose
+        ``CameraTracker.track`` just returned).  ``skip_if``: an int32 device tensor; if its first word is nonzero
+        when the kernel runs, the call changes nothing (the status of an alignment: lost frames stay out)."""
+        fx, fy, cx, cy = _camera(K)
+        d = _depth_tensor(depth, self.device, 3)
+        if d.shape[0] != 1:
+            raise ValueError(f"depth must be one [H, W] image, got {tuple(d.shape)}")
+        if skip_if is not None:
+            if not isinstance(skip_if, torch.Tensor) or skip_if.dtype != torch.int32 or skip_if.numel() < 1:
+                raise TypeError("skip_if must be an int32 tensor on the volume's device")
+            if skip_if.device != d.device:
+                raise ValueError(f"skip_if on {skip_if.device}, the volume on {d.device}")
+        T = self._pose(T_sensor_to_map)
+        tensors = (self.volume, d, T) + (() if skip_if is None else (skip_if,))
+        _lib.require_gpu(*tensors)
+        _lib.check(_lib.lib().mf_tsdf_integrate(
+            _lib.ptr(self.volume), *self.dims, *self.origin, self.pitch, self.truncation, self.max_weight, _lib.ptr(d),
+            int(d.shape[1]), int(d.shape[2]), fx, fy, cx, cy, _lib.ptr(T), _lib.ptr(skip_if), _lib.stream_ptr()),
+            "mf_tsdf_integrate")
+        return self
+
+    def raycast(self, K, T_sensor_to_map, height, width, step=None, min_depth=0.0, max_depth=None, return_code=False):
+        """The fused surface seen through ``K`` from ``T_sensor_to_map``: a float32 [height, width] device tensor of
+        camera-frame depths, 0 where the ray finds no surface (the tracker's "no depth").  The ray is sampled every
+        ``step`` metres of depth (default ``truncation / 2``) between ``min_depth`` and ``max_depth`` (default: no
+        limit) inside the volume and the zero crossing is interpolated between the two samples around it.  With
+        ``return_code`` also a uint8 image of how each ray ended (``RAY_HIT`` .. ``RAY_CAP``)."""
+        fx, fy, cx, cy = _camera(K)
+        height, width = int(height), int(width)
+        if height < 1 or width < 1:
+            raise ValueError(f"height x width = {height} x {width}: each >= 1")
+        step = self.truncation / 2.0 if step is None else float(step)
+        if not step > 0:
+            raise ValueError(f"step = {step}: must be > 0")
+        min_depth = float(min_depth)
+        max_depth = math.inf if max_depth is None else float(max_depth)
+        if not 0 <= min_depth < max_depth:
+            raise ValueError(f"min_depth = {min_depth}, max_depth = {max_depth}: 0 <= min_depth < max_depth")
+        max_steps = self.max_steps(step)
+        if max_steps > MAX_STEPS:
+            raise ValueError(f"step = {step}: {max_steps} samples per ray, at most {MAX_STEPS}")
+        T = self._pose(T_sensor_to_map)
+        depth = torch.empty((height, width), dtype=torch.float32, device=self.device)
+        code = torch.empty((height, width), dtype=torch.uint8, device=self.device) if return_code else None
+        _lib.require_gpu(self.volume, T, depth)
+        _lib.check(_lib.lib().mf_tsdf_raycast(
+            _lib.ptr(self.volume), *self.dims, *self.origin, self.pitch, step, min_depth, max_depth, max_steps,
+            height, width, fx, fy, cx, cy, _lib.ptr(T), _lib.ptr(depth), _lib.ptr(code), _lib.stream_ptr()),
+            "mf_tsdf_raycast")
+        return (depth, code) if return_code else depth
+
+
+class ModelTracker:
+    """Track a depth sequence of ``height`` x ``width`` images against the fused model in ``volume``.
+
+    ``track(depth)`` returns ``T_cur_to_map`` (a float64 [4, 4] device tensor).  The first call integrates the image
+    at ``T_first`` (default: the identity) and returns ``T_first``.  Every later call ray-casts the volume from the
+    last pose, installs that render as the reference of its ``CameraTracker`` (``set_reference``), aligns the image
+    to it starting from the last pose and integrates the image at the pose found -- unless the alignment was lost:
+    the kernel reads the tracker's status word on the device and leaves the model untouched, and the pose returned is
+    the last one (``CameraTracker`` restores the initial pose).  Nothing is read back in the loop.
+    ``tracker_kwargs`` go to ``CameraTracker`` (levels, iterations, block_band, the thresholds, min_pairs).
+
+    ``status`` / ``lost`` / ``stats`` are the inner tracker's, read back only when asked for."""
+
+    def __init__(self, K, height, width, volume, T_first=None, **tracker_kwargs):
+        if not isinstance(volume, TsdfVolume):
+            raise TypeError(f"volume must be a TsdfVolume, got {type(volume).__name__}")
+        for name in ("reference", "device"):
+            if name in tracker_kwargs:
+                raise TypeError(f"{name} is fixed by ModelTracker: the reference is the model, the device the volume's")
+        _camera(K)
+        self.K, self.height, self.width, self.volume = K, int(height), int(width), volume
+        self.tracker = CameraTracker(K, height, width, reference="first", T_first=T_first, device=volume.device,
+                                     **tracker_kwargs)
+        self._T_first = _pose_tensor(np.eye(4) if T_first is None else T_first, 1, volume.device, "T_first")[0].clone()
+        self._T_last = None
+
+    def track(self, depth):
+        d = self.tracker._depth(depth)[0]
+        if self._T_last is None:
+            self.volume.integrate(d, self.K, self._T_first)
+            self._T_last = self._T_first
+            return self._T_last.clone()
+        reference = self.volume.raycast(self.K, self._T_last, self.height, self.width)
+        self.tracker.set_reference(reference, self._T_last)
+        T = self.tracker.track(d, T_init=self._T_last)
+        self.volume.integrate(d, self.K, T, skip_if=self.tracker._al.status)  # (the device word: no read-back)
+        self._T_last = T
+        return T.clone()
+
+    @property
+    def status(self):
+        return self.tracker.status
+
+    @property
+    def lost(self):
+        return self.tracker.lost
+
+    @property
+    def stats(self):
+        return self.tracker.stats
