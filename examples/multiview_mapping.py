@@ -4,12 +4,14 @@ integrate_tracked_frame (one occupancy map per stable id) -> target grids -> Mod
 object is spawned once three of its poses agree).  Prints the id table of every frame.
 
     python examples/multiview_mapping.py [--frames 3] [--model <chainer .npz checkpoint>]
-                                       [--track-camera | --track-model]
+                                       [--track-camera | --track-model [--save-mesh PATH]]
 
 --track-camera: the sensor pose is CameraTracker.track(depth) (dense depth alignment, frame to frame, anchored at frame
 0's pose) instead of the sequence's ground truth; its error against the ground truth is printed per frame.
 --track-model: the same through ModelTracker: every frame is aligned to a ray-cast of the TSDF volume that the earlier
 frames were fused into (1 cm voxels over the scene), frame to model instead of frame to frame.
+--save-mesh PATH (with --track-model): after the last frame the fused model is written as a Wavefront OBJ
+(TsdfVolume.extract_mesh, geometry.save_obj).
 """
 import argparse
 import os
@@ -48,9 +50,12 @@ def main():
     ap.add_argument("--track-camera", action="store_true", help="estimate the sensor pose from the depth images")
     ap.add_argument("--track-model", action="store_true",
                     help="estimate the sensor pose by aligning every frame to the fused TSDF model")
+    ap.add_argument("--save-mesh", metavar="PATH", help="with --track-model: write the fused model as an OBJ")
     args = ap.parse_args()
     if args.track_camera and args.track_model:
         ap.error("--track-camera or --track-model, not both")
+    if args.save_mesh and not args.track_model:
+        ap.error("--save-mesh needs --track-model")
     frames = morefusion.synthetic.make_tracking_sequence(0, args.frames)
     models = PitchTableModels()
     pitch_of = lambda c: models.get_voxel_pitch(32, int(c))  # noqa: E731
@@ -118,6 +123,10 @@ def main():
         for i, c, pose in zip(ids.tolist(), class_id.tolist(), T_cad2map):
             voter.append_pose(i, c, pose)
         print(f"frame {k}: {len(ids)} poses, spawned objects {voter.validate()}")
+    if args.save_mesh:
+        vertices, faces = camera.volume.extract_mesh()
+        morefusion.geometry.save_obj(args.save_mesh, vertices, faces)
+        print(f"fused model: {len(vertices)} vertices, {len(faces)} faces -> {args.save_mesh}")
     stable = sum(len(t) == 1 for t in ids_of_object.values())
     print(f"stable ids: {stable} of {len(ids_of_object)} objects")
 

@@ -7,7 +7,7 @@ grid_target / grid_noentry, as collision_based_pose_refinement.py passes them.  
 before and after the refinement.
 
     python examples/online_pose_refinement.py [--frames 3] [--model <chainer .npz checkpoint>] [--render-service]
-                                              [--track-camera | --track-model]
+                                              [--track-camera | --track-model [--save-mesh PATH]]
 
 --render-service: the tracker matches against the reference's render-service route (use_render_service,
 OctomapServer.cpp:126-135) -- OctomapServer.grids_in_map_frame meshed and rasterised (contrib.render_voxel_grids) --
@@ -17,6 +17,8 @@ alignment, frame to frame, anchored at frame 0's pose) instead of the sequence's
 ground truth is printed per frame.
 --track-model: the same through ModelTracker: every frame is aligned to a ray-cast of the TSDF volume that the earlier
 frames were fused into (1 cm voxels over the scene), frame to model instead of frame to frame.
+--save-mesh PATH (with --track-model): after the last frame the fused model is written as a Wavefront OBJ
+(TsdfVolume.extract_mesh, geometry.save_obj).
 """
 import argparse
 import os
@@ -57,9 +59,12 @@ def main():
     ap.add_argument("--track-camera", action="store_true", help="estimate the sensor pose from the depth images")
     ap.add_argument("--track-model", action="store_true",
                     help="estimate the sensor pose by aligning every frame to the fused TSDF model")
+    ap.add_argument("--save-mesh", metavar="PATH", help="with --track-model: write the fused model as an OBJ")
     args = ap.parse_args()
     if args.track_camera and args.track_model:
         ap.error("--track-camera or --track-model, not both")
+    if args.save_mesh and not args.track_model:
+        ap.error("--save-mesh needs --track-model")
     frames = morefusion.synthetic.make_tracking_sequence(0, args.frames)
     models = PitchTableModels()
     pitch_of = lambda c: models.get_voxel_pitch(32, int(c))  # noqa: E731
@@ -104,6 +109,10 @@ def main():
         server.insert_scan(tracker.pts_map.reshape(pcd.shape), tracked, class_of, pitch_of, origin=T[:3, 3])
         grids = server.publish_grids(T)
         print(f"frame {k} ({tracker.render}): maps {server.mapping.instance_ids}, published {grids['instance_ids']}")
+    if args.save_mesh:
+        vertices, faces = camera.volume.extract_mesh()
+        morefusion.geometry.save_obj(args.save_mesh, vertices, faces)
+        print(f"fused model: {len(vertices)} vertices, {len(faces)} faces -> {args.save_mesh}")
     # the pose stage of the last frame, in the sensor frame: crops -> the server's grids -> the network
     published = grids["instance_ids"]
     crops = morefusion.geometry.instance_crops(to_gpu(f["rgb"]), to_gpu(f["depth"]), K, tracked,

@@ -1452,6 +1452,61 @@ int mf_tsdf_raycast(const float *volume, int32_t nx, int32_t ny, int32_t nz, dou
                     int32_t max_steps, int32_t H, int32_t W, double fx, double fy, double cx, double cy,
                     const double *T_sensor_to_map, float *depth_out, uint8_t *code_out, mfStream_t stream);
 
+/* ---- TSDF mesh: the fused surface as a welded triangle mesh with normals (contrib/tsdf_volume.py, csrc/tsdfmesh.hip) ----
+ * TsdfVolume.extract_mesh (DESIGN.md "TSDF mesh"; tests/tsdfmesh_ref.py is the NumPy mirror, bit for bit, written
+ * from this text).  All arrays are DEVICE arrays (totals too); every call is asynchronous on `stream`, allocates
+ * nothing and never synchronises.  VOLUME, origin and pitch are those of "TSDF fusion": lattice point (i, j, k) sits at
+ * p_a = origin_a + pitch * double(index_a) and has the pair (F, W) = (tsdf, weight).
+ *
+ * INSIDE: a point is inside iff F <= 0 (-0.0 is inside, a NaN is not).  OBSERVED: a point is observed iff
+ * double(W) >= min_weight (min_weight > 0); cell (i, j, k), 0 <= i <= nx - 2, 0 <= j <= ny - 2, 0 <= k <= nz - 2, with
+ * the corners (i + dx, j + dy, k + dz), is observed iff its eight corners are.  Only observed cells have faces.
+ *
+ * TRIANGULATION: the six-tetrahedra subdivision written at the head of csrc/gridmesh.hip, "occupied" read as inside.
+ * Corner codes are dx * 4 + dy * 2 + dz.  Tetrahedron t = 0 .. 5 walks the axes xyz, xzy, yxz, yzx, zxy, zyx: its
+ * corners are c0 = the cell, c1 = c0 + e_a, c2 = c1 + e_b, c3 = the cell + (1, 1, 1).  With e(i, j) the vertex on the
+ * edge between corners i and j of the tetrahedron:
+ *   one corner i alone on its side:          (e(i, j0), e(i, j1), e(i, j2)), j ascending;
+ *   corners a < b inside, c < d outside:     (e(a, c), e(a, d), e(b, d)) then (e(a, c), e(b, d), e(b, c));
+ * the last two vertices of a triangle are exchanged where that makes it counter-clockwise seen from the outside.
+ * Degenerate triangles (a tsdf of exactly 0 at a corner) are kept.
+ *
+ * VERTICES: point (i, j, k) owns the edges towards + (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1),
+ * directions 0 .. 6.  An owned edge whose other end is a lattice point carries a vertex iff its ends differ in
+ * inside / outside and at least one observed cell contains it; the cells that contain the edge are (i, j, k) - s with
+ * s in {0, 1} on every axis where the direction's component is 0 (s = 0 elsewhere), those that are cells.  Vertices are
+ * numbered by rank in ascending (k, j, i, direction) order, faces in ascending (k, j, i, tetrahedron, triangle) order of
+ * their cell; faces are int32 [n_faces][3] indices into vertices float64 [n_vertices][3].
+ *
+ * POSITION, float64, + - * / only, nothing contracted, associated as written; a = the owner, b = the other end:
+ *   r = double(F_a) / (double(F_a) - double(F_b))
+ *   v_c = p_a,c + r * (p_b,c - p_a,c)                      (p as above, c = x, y, z)
+ * NORMAL (normals float64 [n_vertices][3], may be null), towards positive tsdf.  At a lattice point q, per axis c with
+ * q+ and q- its neighbours along c ("usable": a lattice point that is observed), F the widened tsdf:
+ *   both usable: G_c = (F(q+) - F(q-)) / 2;  only q+: G_c = F(q+) - F(q);  only q-: G_c = F(q) - F(q-);  neither: 0.
+ * At the vertex:
+ *   g_c = G_c(a) + r * (G_c(b) - G_c(a));   s = (g_x * g_x + g_y * g_y) + g_z * g_z
+ *   n_c = g_c / sqrt(s) if s > 0, else n = (0, 0, 0)      (sqrt and / correctly rounded)
+ *
+ * WORKSPACE of mf_tsdfmesh_workspace_bytes(nx, ny, nz) bytes, 16-byte aligned, three parts that each start at a multiple
+ * of 16: flags uint8 [nz][ny][nx] (bit 0 inside, bit 1 observed), masks uint8 [nz][ny][nx] (bit d: the owned edge of
+ * direction d carries a vertex), rows int64 [nz ny + 1][2] (vertices, faces before row (k, j), row index k ny + j; the
+ * last entry holds the totals).  mf_tsdfmesh_count fills all three; mf_tsdfmesh_emit reads them.
+ * Refused with -hipErrorInvalidValue (the function's name in mf_last_error_string) unless: nx, ny, nz >= 2 and
+ * nx ny nz < 2^31; min_weight > 0; pitch > 0; 0 <= n_vertices, n_faces < 2^31; the arrays non-null (normals may be
+ * null), the volume and the workspace 16-byte aligned. */
+/* Host-only: the workspace's bytes; < 0 for a bad volume. */
+int64_t mf_tsdfmesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+/* Three launches (flags, masks and row counts, scan of the rows): totals int64 [2] = (n_vertices, n_faces). */
+int mf_tsdfmesh_count(const float *volume, int32_t nx, int32_t ny, int32_t nz, double min_weight, void *workspace,
+                      int64_t *totals, mfStream_t stream);
+/* One launch, a workgroup per row (k, j): writes every vertex (and normal) and every face.  workspace as
+ * mf_tsdfmesh_count of the same volume and min_weight left it, n_vertices and n_faces its totals (rows past them are
+ * not written). */
+int mf_tsdfmesh_emit(const float *volume, int32_t nx, int32_t ny, int32_t nz, double origin_x, double origin_y,
+                     double origin_z, double pitch, double min_weight, const void *workspace, int64_t n_vertices,
+                     int64_t n_faces, double *vertices, int32_t *faces, double *normals, mfStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

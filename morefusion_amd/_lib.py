@@ -268,6 +268,9 @@ _SIGNATURES = {
     "mf_camtrack_align": ([_p, _p] + [_i] * 4 + [_d] * 4 + [_p, _p, _p, _d, _d, _i] + [_p] * 6, _i),
     "mf_tsdf_integrate": ([_p] + [_i] * 3 + [_d] * 6 + [_p, _i, _i] + [_d] * 4 + [_p, _p, _p], _i),
     "mf_tsdf_raycast": ([_p] + [_i] * 3 + [_d] * 7 + [_i] * 3 + [_d] * 4 + [_p] * 4, _i),
+    "mf_tsdfmesh_workspace_bytes": ([_i] * 3, _i64),
+    "mf_tsdfmesh_count": ([_p] + [_i] * 3 + [_d, _p, _p, _p], _i),
+    "mf_tsdfmesh_emit": ([_p] + [_i] * 3 + [_d] * 5 + [_p, _i64, _i64] + [_p] * 4, _i),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

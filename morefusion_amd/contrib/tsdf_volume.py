@@ -8,7 +8,8 @@ ISMAR 2011) removes both: ``TsdfVolume.integrate`` fuses each frame into a volum
 estimated pose, ``TsdfVolume.raycast`` renders the fused surface from any pose with sub-voxel depth, and
 ``ModelTracker`` hands that render to ``CameraTracker.set_reference`` before every alignment.
 
-* ``TsdfVolume``: the volume and its two kernels.
+* ``TsdfVolume``: the volume and its two kernels; ``extract_mesh`` takes the fused surface out as a triangle mesh
+  with normals (csrc/tsdfmesh.hip, ``mf_tsdfmesh_*``, DESIGN.md "TSDF mesh").
 * ``ModelTracker``: ray-cast, align, integrate per frame; no host synchronisation in the loop, and a lost alignment is
   kept out of the model by the device status word, not by reading it back.
 """
@@ -135,6 +136,39 @@ class TsdfVolume:
             height, width, fx, fy, cx, cy, _lib.ptr(T), _lib.ptr(depth), _lib.ptr(code), _lib.stream_ptr()),
             "mf_tsdf_raycast")
         return (depth, code) if return_code else depth
+
+    def extract_mesh(self, min_weight=1.0, normals=False):
+        """The fused surface as a welded triangle mesh (csrc/tsdfmesh.hip, include/mfhip.h "TSDF mesh"): ``(vertices
+        float64 [V, 3], faces int32 [F, 3])`` on the volume's device, in the map frame, plus ``normals`` float64
+        [V, 3] (unit, towards positive tsdf: out of the surface) when asked for.  The surface is the zero level of
+        the tsdf (``tsdf <= 0`` is inside) over the six-tetrahedra subdivision of the cells whose eight corners all
+        have ``weight >= min_weight``: what the camera never saw is left out, so the mesh is open where the
+        observation ends.  Faces are counter-clockwise seen from the outside; vertex and face order are fixed by the
+        volume alone.  One read-back: the two totals, to size the outputs.  An empty surface gives empty tensors."""
+        min_weight = float(min_weight)
+        if not min_weight > 0:
+            raise ValueError(f"min_weight = {min_weight}: must be > 0")
+        L = _lib.lib()
+        nbytes = L.mf_tsdfmesh_workspace_bytes(*self.dims)
+        if nbytes < 0:
+            raise ValueError(f"dims = {self.dims}: refused by mf_tsdfmesh_workspace_bytes")
+        workspace = torch.empty(nbytes // 8 + 2, dtype=torch.float64, device=self.device)
+        totals = torch.empty(2, dtype=torch.int64, device=self.device)
+        _lib.require_gpu(self.volume, workspace, totals)
+        _lib.check(L.mf_tsdfmesh_count(_lib.ptr(self.volume), *self.dims, min_weight, _lib.ptr(workspace),
+                                       _lib.ptr(totals), _lib.stream_ptr()), "mf_tsdfmesh_count")
+        n_vertices, n_faces = totals.cpu().tolist()  # the call's read-back
+        if n_vertices >= 1 << 31 or n_faces >= 1 << 31:
+            raise ValueError(f"{n_vertices} vertices, {n_faces} faces: each must be below 2^31")
+        vertices = torch.empty((n_vertices, 3), dtype=torch.float64, device=self.device)
+        faces = torch.empty((n_faces, 3), dtype=torch.int32, device=self.device)
+        normal = torch.empty((n_vertices, 3), dtype=torch.float64, device=self.device) if normals else None
+        if n_vertices > 0:
+            _lib.check(L.mf_tsdfmesh_emit(
+                _lib.ptr(self.volume), *self.dims, *self.origin, self.pitch, min_weight, _lib.ptr(workspace),
+                n_vertices, n_faces, _lib.ptr(vertices), _lib.ptr(faces), _lib.ptr(normal), _lib.stream_ptr()),
+                "mf_tsdfmesh_emit")
+        return (vertices, faces, normal) if normals else (vertices, faces)
 
 
 class ModelTracker:

@@ -60,6 +60,21 @@ def load_obj(path):
     return v, f.astype(np.int32)
 
 
+def save_obj(path, vertices, faces):
+    """(vertices [V, 3], faces [F, 3]; NumPy or tensors) -> a Wavefront OBJ of ``v`` and ``f`` lines that ``load_obj``
+    reads back: faces exactly, vertices to the 17 significant digits written (every float64 survives them)."""
+    v = vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else np.asarray(vertices)
+    f = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
+    v, f = v.astype(np.float64).reshape(-1, 3), f.astype(np.int64).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError(f"face index outside the {len(v)} vertices")
+    with open(path, "w") as fh:
+        for x, y, z in v.tolist():
+            fh.write(f"v {x:.17g} {y:.17g} {z:.17g}\n")
+        for a, b, c in f.tolist():
+            fh.write(f"f {a + 1} {b + 1} {c + 1}\n")
+
+
 def _device(x, device):
     if device is not None:
         return torch.device(device)
