@@ -313,7 +313,12 @@ int mf_sparse_conv3d_k4s2_fwd(const float *x, const int32_t *counts, const float
  *   nn_idx [B,P,M] int32 (may be NULL): arg-min indices of the ADD-S rows, written by _fwd and
  *   read by _bwd (NULL: _bwd searches again).
  * _bwd: gT_pred [B,P,4,4] = d(sum gout * out) / d T_pred (rows 0..2; row 3 = 0).  The true
- * pose and the model points receive no gradient (they are data in the reference's callers). */
+ * pose and the model points receive no gradient (they are data in the reference's callers).
+ * A point whose residual is exactly zero adds nothing to the gradient.  A predicted pose with a
+ * non-finite entry gives out = NaN; no candidate of its ADD-S search compares below +inf, so its
+ * nn_idx row holds 0 wherever the query is NaN (the first-minimum rule over NaN distances), and
+ * its gT_pred rows are zeros (a NaN distance is not > 0).  B <= 0 or P <= 0: nothing to do,
+ * returns 0; M <= 0: -hipErrorInvalidValue (-1) before any launch. */
 int mf_average_distance_fwd(const float *points, const float *T_true, const float *T_pred,
                             const uint8_t *symmetric, int32_t B, int32_t M, int32_t P,
                             float *out, int32_t *nn_idx, mfStream_t stream);
@@ -702,7 +707,10 @@ int mf_psp_tail_rows_bf16_bwd(const void *grows, const int64_t *pix, int32_t B, 
 
 /* The confidence terms of the pose loss and their reduction (contrib/singleview_3d/models/model.py:417-434):
  * loss[0] = mean over objects of the mean over confident points (conf > 0) of add * conf - lambda * log(conf);
- * cnt [B] is kept for the backward (dadd, dconf [B, P] from the scalar gradient gloss[0]). */
+ * cnt [B] is kept for the backward (dadd, dconf [B, P] from the scalar gradient gloss[0]).  An object without a
+ * confident point has cnt = 0 and the value 0 / 0 = NaN, which makes loss[0] NaN; its dadd / dconf rows are zeros (as
+ * is every entry with conf <= 0) and the other objects' gradients stay finite.  _fwd with B outside 1 .. 8192 or
+ * P < 1 returns -hipErrorInvalidValue (-1) before any launch and writes nothing; _bwd with B < 1 or P < 1 returns 0. */
 int mf_confidence_loss_fwd(const float *add, const float *conf, int32_t B, int32_t P, float lambda, float *loss,
                            int32_t *cnt, mfStream_t stream);
 int mf_confidence_loss_bwd(const float *add, const float *conf, const int32_t *cnt, const float *gloss, int32_t B,
@@ -710,7 +718,9 @@ int mf_confidence_loss_bwd(const float *add, const float *conf, const int32_t *c
 
 /* Pose epilogue of the TRAINING path (model.py:262-273: class selection, F.normalize, translation, sigmoid) on the
  * three heads' fp32 outputs orot [n, 4 n_fg], otrn [n, 3 n_fg], ocnf [n, n_fg]; the backward writes the three gradient
- * row blocks completely.  One launch each (torch: ~27 / ~47 incl. three index_put sorts). */
+ * row blocks completely.  One launch each (torch: ~27 / ~47 incl. three index_put sorts).  rot = x / (|x| + 1e-5)
+ * (an all-zero quaternion row gives zeros forward and g / 1e-5 backward).  An object whose class_id is outside
+ * 1 .. n_fg has no head: its rot / trans / conf are NaN and its gradient rows are zeros, whatever the cotangents. */
 int mf_pose_epilogue_train_fwd(const float *orot, const float *otrn, const float *ocnf, const int64_t *class_id,
                                const float *pts, const float *origin, const float *pitch, int32_t B, int32_t P,
                                int32_t n_fg, float *rot, float *trans, float *conf, mfStream_t stream);
