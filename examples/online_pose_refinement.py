@@ -7,7 +7,8 @@ grid_target / grid_noentry, as collision_based_pose_refinement.py passes them.  
 before and after the refinement.
 
     python examples/online_pose_refinement.py [--frames 3] [--model <chainer .npz checkpoint>] [--render-service]
-                                              [--track-camera | --track-model [--save-mesh PATH]]
+                                              [--track-camera | --track-model [--save-mesh PATH]
+                                               [--grids-from-model]]
 
 --render-service: the tracker matches against the reference's render-service route (use_render_service,
 OctomapServer.cpp:126-135) -- OctomapServer.grids_in_map_frame meshed and rasterised (contrib.render_voxel_grids) --
@@ -17,6 +18,10 @@ alignment, frame to frame, anchored at frame 0's pose) instead of the sequence's
 ground truth is printed per frame.
 --track-model: the same through ModelTracker: every frame is aligned to a ray-cast of the TSDF volume that the earlier
 frames were fused into (1 cm voxels over the scene), frame to model instead of frame to frame.
+--grids-from-model (with --track-model): the volume is an InstanceTsdfVolume, ModelTracker.track(depth, label) fuses the
+tracked labels of every frame next to its depth, and the grids of the pose stage are InstanceTsdfVolume.publish_grids
+(the fused model, the same dict) instead of OctomapServer.publish_grids.  The server is still filled: the instance
+tracker matches its detections against the server's maps.
 --save-mesh PATH (with --track-model): after the last frame the fused model is written as a Wavefront OBJ
 (TsdfVolume.extract_mesh, geometry.save_obj).
 """
@@ -40,9 +45,9 @@ MODEL_VOLUME = dict(dims=(161, 121, 93), pitch=0.01, origin=(-0.8, 0.3, -0.1))
 TO_GROUND = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0.2], [0, 0, 0, 1]], np.float64)
 
 
-def track_camera(camera, depth, T_true, k):
+def track_camera(camera, depth, T_true, k, **labels):
     """CameraTracker's (or ModelTracker's) pose of the frame, and its error against the ground truth on stdout."""
-    T = camera.track(depth).cpu().numpy()
+    T = camera.track(depth, **labels).cpu().numpy()
     D = np.linalg.inv(T_true) @ T
     angle = np.degrees(np.arccos(np.clip((np.trace(D[:3, :3]) - 1) / 2, -1, 1)))
     state = "" if k == 0 else (" LOST" if camera.lost else f" ({int(camera.stats[-1, 0])} pairs)")
@@ -60,11 +65,16 @@ def main():
     ap.add_argument("--track-model", action="store_true",
                     help="estimate the sensor pose by aligning every frame to the fused TSDF model")
     ap.add_argument("--save-mesh", metavar="PATH", help="with --track-model: write the fused model as an OBJ")
+    ap.add_argument("--grids-from-model", action="store_true",
+                    help="with --track-model: fuse the tracked labels into the TSDF volume and take the pose stage's "
+                         "grids from it (InstanceTsdfVolume.publish_grids) instead of from the map server")
     args = ap.parse_args()
     if args.track_camera and args.track_model:
         ap.error("--track-camera or --track-model, not both")
     if args.save_mesh and not args.track_model:
         ap.error("--save-mesh needs --track-model")
+    if args.grids_from_model and not args.track_model:
+        ap.error("--grids-from-model needs --track-model")
     frames = morefusion.synthetic.make_tracking_sequence(0, args.frames)
     models = PitchTableModels()
     pitch_of = lambda c: models.get_voxel_pitch(32, int(c))  # noqa: E731
@@ -95,20 +105,43 @@ def main():
                                                   T_first=TO_GROUND @ frames[0]["T_sensor_to_map"])
     if args.track_model:
         height, width = frames[0]["depth"].shape
-        camera = morefusion.contrib.ModelTracker(frames[0]["K"], height, width,
-                                                 morefusion.contrib.TsdfVolume(**MODEL_VOLUME),
+        volume = (morefusion.contrib.InstanceTsdfVolume if args.grids_from_model else morefusion.contrib.TsdfVolume)
+        camera = morefusion.contrib.ModelTracker(frames[0]["K"], height, width, volume(**MODEL_VOLUME),
                                                  T_first=TO_GROUND @ frames[0]["T_sensor_to_map"])
+    classes = {}  # instance id -> class id, over the frames so far
     for k, f in enumerate(frames):
         K, T = f["K"], TO_GROUND @ f["T_sensor_to_map"]
-        if camera is not None:
-            T = track_camera(camera, to_gpu(f["depth"]), T, k)
         pcd = morefusion.geometry.pointcloud_from_depth(f["depth"], K[0, 0], K[1, 1], K[0, 2], K[1, 2])
-        tracked, _, class_of, _ = tracker.track(to_gpu(pcd.astype(np.float32)), to_gpu(f["label_detected"]),
-                                                f["class_ids_by_detection"], K, T,
-                                                depth=to_gpu(f["depth"]) if args.render_service else None)
+
+        def track_instances(T):
+            return tracker.track(to_gpu(pcd.astype(np.float32)), to_gpu(f["label_detected"]),
+                                 f["class_ids_by_detection"], K, T,
+                                 depth=to_gpu(f["depth"]) if args.render_service else None)
+
+        if args.grids_from_model:
+            found = []  # the labels need the frame's pose: ModelTracker asks for them once it has aligned the frame
+
+            def label_at(T_device):
+                found.append(track_instances(T_device.cpu().numpy()))
+                return found[0][0]
+
+            T = track_camera(camera, to_gpu(f["depth"]), T, k, label=label_at)
+            tracked, _, class_of, _ = found[0]
+        else:
+            if camera is not None:
+                T = track_camera(camera, to_gpu(f["depth"]), T, k)
+            tracked, _, class_of, _ = track_instances(T)
+        classes.update({int(i): int(c) for i, c in class_of.items()})
         server.insert_scan(tracker.pts_map.reshape(pcd.shape), tracked, class_of, pitch_of, origin=T[:3, 3])
-        grids = server.publish_grids(T)
-        print(f"frame {k} ({tracker.render}): maps {server.mapping.instance_ids}, published {grids['instance_ids']}")
+        if args.grids_from_model:
+            ids = sorted(classes)
+            grids = camera.volume.publish_grids(T, ids, pitch={i: pitch_of(classes[i]) for i in ids}, class_ids=classes,
+                                                ground_z=0.0 if server.ground_as_noentry else None,
+                                                free_as_noentry=server.free_as_noentry)
+        else:
+            grids = server.publish_grids(T)
+        source = "model" if args.grids_from_model else tracker.render
+        print(f"frame {k} ({source}): maps {server.mapping.instance_ids}, published {grids['instance_ids']}")
     if args.save_mesh:
         vertices, faces = camera.volume.extract_mesh()
         morefusion.geometry.save_obj(args.save_mesh, vertices, faces)

@@ -1517,6 +1517,73 @@ int mf_tsdfmesh_emit(const float *volume, int32_t nx, int32_t ny, int32_t nz, do
                      double origin_z, double pitch, double min_weight, const void *workspace, int64_t n_vertices,
                      int64_t n_faces, double *vertices, int32_t *faces, double *normals, mfStream_t stream);
 
+/* ---- TSDF labels: an instance label per voxel, and the pose stages' grids from it (contrib/instance_tsdf_volume.py,
+ * csrc/tsdflabel.hip) ----
+ * InstanceTsdfVolume (DESIGN.md "TSDF labels"; tests/tsdflabel_ref.py is the NumPy mirror, bit for bit, written from
+ * this text).  All arrays are DEVICE arrays; every call is asynchronous on `stream`, allocates nothing and never
+ * synchronises.  VOLUME, origin, pitch, POSE and ARITHMETIC are those of "TSDF fusion"; integers are int32 unless said
+ * otherwise, and there are no float atomics: every result is independent of the order in which lanes run.
+ *
+ * LABELS: int32 [nz][ny][nx][2], the pair (label, count) of voxel (i, j, k) at int index 2 ((k ny + j) nx + i): the
+ * volume's voxel order, 8 bytes per voxel.  A fresh volume is (0, 0) everywhere; the caller fills it.  count >= 0, and
+ * count == 0 goes with label == 0.
+ * VOTES: a pixel label v votes iff v >= 1 (a tracked instance id) or v == -1 (the background); -2 ("uncertain"), 0 and
+ * everything below -2 cast no vote.
+ * A position is INSIDE the volume iff g_a = floor((m_a - origin_a) / pitch + 0.5) satisfies g_a >= 0 and g_a <= n_a - 1
+ * on every axis (compared as float64; a NaN is outside); its voxel is (g_x, g_y, g_z).
+ * A rigid transform T (float64 [16] row-major on the device, 12 words read) moves p to
+ *   T p := ((T[4 a] p_x + T[4 a + 1] p_y) + T[4 a + 2] p_z) + T[4 a + 3],  a = x, y, z.
+ * Refused with -hipErrorInvalidValue (the function's name in mf_last_error_string) unless: nx, ny, nz >= 2 and
+ * nx ny nz < 2^31; pitch > 0; truncation > 0; max_weight >= 1; 1 <= H, W <= MF_RENDER_MAX_SIDE; fx, fy > 0;
+ * max_count >= 1; min_count >= 1; min_weight > 0; 1 <= B <= MF_TSDF_MAX_INSTANCES; 1 <= D <= MF_TSDF_MAX_GRID_DIM;
+ * flags in 0 .. 3; the arrays non-null (skip_flag may be null). */
+#define MF_TSDF_MAX_INSTANCES 64
+#define MF_TSDF_MAX_GRID_DIM 256
+/* mf_tsdf_integrate of the same arguments -- the (tsdf, weight) bytes it leaves are the same -- and one vote per voxel.
+ * One lane per voxel; if skip_flag is non-null and *skip_flag != 0 neither array is written.  A voxel votes iff it
+ * passed every requirement of mf_tsdf_integrate (it was written), sdf <= truncation (sdf as there, before the clamp)
+ * and v = label_image[row][col] (int32 [H][W], the pixel its depth came from) is a voting label.  With (l, c) its pair:
+ *   c == 0:     (l, c) = (v, 1)
+ *   l == v:     c = min(c + 1, max_count)
+ *   otherwise:  c = c - 1, and if c == 0 then l = 0. */
+int mf_tsdf_integrate_labels(float *volume, int32_t *labels, int32_t nx, int32_t ny, int32_t nz, double origin_x,
+                             double origin_y, double origin_z, double pitch, double truncation, double max_weight,
+                             const float *depth, int32_t H, int32_t W, double fx, double fy, double cx, double cy,
+                             const double *T_sensor_to_map, const int32_t *label_image, int32_t max_count,
+                             const int32_t *skip_flag, mfStream_t stream);
+/* The label under every pixel of a depth image (e.g. mf_tsdf_raycast's depth_out from the same pose).  One lane per
+ * pixel (16 x 16 pixel workgroups); out int32 [H][W] is written for EVERY pixel.  Pixel (row, col) with d =
+ * double(depth[row][col]):  unless d > 0: 0.  q as in mf_tsdf_raycast, the camera point p = (q_0 * d, q_1 * d, d),
+ * m = T_sensor_to_map p.  out = the label of m's voxel if m is inside and its count >= min_count, else 0. */
+int mf_tsdf_label_image(const int32_t *labels, int32_t nx, int32_t ny, int32_t nz, double origin_x, double origin_y,
+                        double origin_z, double pitch, const float *depth, int32_t H, int32_t W, double fx, double fy,
+                        double cx, double cy, const double *T_sensor_to_map, int32_t min_count, int32_t *out,
+                        mfStream_t stream);
+/* Where every instance is.  ids int32 [B] STRICTLY ASCENDING (the caller's duty: an id out of order is not found);
+ * table int64 [B][10] := per id, over the voxels (i, j, k) with double(weight) >= min_weight, tsdf <= 0, label == id
+ * and count >= min_count: {their number, sum i, sum j, sum k, min i, min j, min k, max i, max j, max k}; an id without
+ * a voxel gets {0, 0, 0, 0, nx, ny, nz, -1, -1, -1}.  Two launches: one sets the table, one adds to it (a lane per
+ * voxel, a table per workgroup in LDS, 64-bit integer atomics into `table`). */
+int mf_tsdf_instance_stats(const float *volume, const int32_t *labels, int32_t nx, int32_t ny, int32_t nz,
+                           double min_weight, int32_t min_count, const int32_t *ids, int32_t B, int64_t *table,
+                           mfStream_t stream);
+/* B grids of D^3 voxels in the SENSOR frame, in the index order of mf_occserver_publish (grid [b][x][y][z]); one lane
+ * per output voxel, every output element is written.  Per grid b, with p = grid_pitch[b] (float64 [B]), c =
+ * center_map[b] (float64 [B][3], MAP frame) and id = ids[b]:
+ *   centre = T_map_to_sensor c;  origin[b]_a := centre_a - (double(D) / 2.0 - 0.5) * p      (origin float64 [B][3])
+ *   voxel (x, y, z):  s_a = origin[b]_a + p * double(index_a);  m = T_sensor_to_map s
+ *   1. flags & 1 and m_z < ground_z:                          noentry = 1
+ *   2. else m outside the volume, or not double(weight) >= min_weight of its voxel (F, weight; l, c):   nothing
+ *   3. else F <= 0:  if c >= min_count:  l == id: target = 1;  else l != 0: noentry = 1
+ *   4. else flags & 2 and double(F) >= empty_above:           noentry = 1
+ * grid_target, grid_noentry float32 (0 or 1), grid_nontarget_empty uint8 := noentry != 0. */
+int mf_tsdf_publish_grids(const float *volume, const int32_t *labels, int32_t nx, int32_t ny, int32_t nz,
+                          double origin_x, double origin_y, double origin_z, double pitch, const int32_t *ids,
+                          const double *grid_pitch, const double *center_map, const double *T_map_to_sensor,
+                          const double *T_sensor_to_map, double min_weight, int32_t min_count, double empty_above,
+                          double ground_z, int32_t flags, int32_t B, int32_t D, double *origin, float *grid_target,
+                          float *grid_noentry, uint8_t *grid_nontarget_empty, mfStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

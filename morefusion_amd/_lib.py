@@ -271,6 +271,10 @@ _SIGNATURES = {
     "mf_tsdfmesh_workspace_bytes": ([_i] * 3, _i64),
     "mf_tsdfmesh_count": ([_p] + [_i] * 3 + [_d, _p, _p, _p], _i),
     "mf_tsdfmesh_emit": ([_p] + [_i] * 3 + [_d] * 5 + [_p, _i64, _i64] + [_p] * 4, _i),
+    "mf_tsdf_integrate_labels": ([_p, _p] + [_i] * 3 + [_d] * 6 + [_p, _i, _i] + [_d] * 4 + [_p, _p, _i, _p, _p], _i),
+    "mf_tsdf_label_image": ([_p] + [_i] * 3 + [_d] * 4 + [_p, _i, _i] + [_d] * 4 + [_p, _i, _p, _p], _i),
+    "mf_tsdf_instance_stats": ([_p, _p] + [_i] * 3 + [_d, _i, _p, _i, _p, _p], _i),
+    "mf_tsdf_publish_grids": ([_p, _p] + [_i] * 3 + [_d] * 4 + [_p] * 5 + [_d, _i, _d, _d] + [_i] * 3 + [_p] * 5, _i),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -15,3 +15,4 @@ from .picking_order import SelectPickingOrder, get_picking_order, occlusion_anal
 from .octomap_server import OctomapServer
 from .camera_tracking import CameraTracker, align_depth
 from .tsdf_volume import ModelTracker, TsdfVolume
+from .instance_tsdf_volume import InstanceTsdfVolume

@@ -180,6 +180,7 @@ class ModelTracker:
     to it starting from the last pose and integrates the image at the pose found -- unless the alignment was lost:
     the kernel reads the tracker's status word on the device and leaves the model untouched, and the pose returned is
     the last one (``CameraTracker`` restores the initial pose).  Nothing is read back in the loop.
+    ``track(depth, label)`` also fuses the frame's instance labels; ``volume`` must then be an ``InstanceTsdfVolume``.
     ``tracker_kwargs`` go to ``CameraTracker`` (levels, iterations, block_band, the thresholds, min_pairs).
 
     ``status`` / ``lost`` / ``stats`` are the inner tracker's, read back only when asked for."""
@@ -197,16 +198,24 @@ class ModelTracker:
         self._T_first = _pose_tensor(np.eye(4) if T_first is None else T_first, 1, volume.device, "T_first")[0].clone()
         self._T_last = None
 
-    def track(self, depth):
+    def track(self, depth, label=None):
+        """``label``: the frame's instance labels, fused next to its depth by ``InstanceTsdfVolume.integrate`` under
+        the same device skip word (the labels do not move the camera) -- an integer [H, W] image, or a callable that
+        gets the pose just found (float64 [4, 4] device tensor) and returns one, for labels that are made with the
+        pose.  None: the plain integrate."""
+        if label is not None and not hasattr(self.volume, "labels"):
+            raise TypeError(f"labels need an InstanceTsdfVolume, the volume is a {type(self.volume).__name__}")
+        labelled = lambda T: {} if label is None else dict(label=label(T) if callable(label) else label)  # noqa: E731
         d = self.tracker._depth(depth)[0]
         if self._T_last is None:
-            self.volume.integrate(d, self.K, self._T_first)
+            self.volume.integrate(d, self.K, self._T_first, **labelled(self._T_first))
             self._T_last = self._T_first
             return self._T_last.clone()
         reference = self.volume.raycast(self.K, self._T_last, self.height, self.width)
         self.tracker.set_reference(reference, self._T_last)
         T = self.tracker.track(d, T_init=self._T_last)
-        self.volume.integrate(d, self.K, T, skip_if=self.tracker._al.status)  # (the device word: no read-back)
+        # (the device word: no read-back)
+        self.volume.integrate(d, self.K, T, skip_if=self.tracker._al.status, **labelled(T))
         self._T_last = T
         return T.clone()
 

@@ -8,6 +8,7 @@
 //
 //   k_tsdf_integrate  a lane per voxel, x fastest: a wave reads 64 (tsdf, weight) pairs = 512 contiguous bytes, and
 //                     stores only the voxels the frame touches.  The pose and the skip word are read from the device.
+//                     The voxel body is tsdf_voxel.h's, shared with the labelled integrate of csrc/tsdflabel.hip.
 //   k_tsdf_raycast    a lane per pixel in 16 x 16 tiles: neighbouring rays sample the same voxels (L2 / L1 hits).
 //                     A sample is 4 loads of 16 bytes (the two x-neighbours are adjacent in memory).
 //
@@ -16,26 +17,15 @@
 #include <math.h>
 
 #include "mf_common.h"
+#include "tsdf_voxel.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kTile = 16;
 
-struct Pose {
-  double R[9], t[3];
-};
-
-__device__ __forceinline__ Pose load_pose(const double *__restrict__ T) {
-  Pose p;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int b = 0; b < 3; ++b) p.R[3 * a + b] = T[4 * a + b];
-    p.t[a] = T[4 * a + 3];
-  }
-  return p;
-}
+using mf_tsdf::Pose;
+using mf_tsdf::load_pose;
 
 // two x-neighbours of the volume: (tsdf, weight) of voxel i and of voxel i + 1 -- 16 bytes at an 8-byte aligned address
 struct __attribute__((aligned(8))) VoxelPair {
@@ -50,31 +40,10 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_integrate(
   const int64_t n = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (n >= n_voxels) return;
   const Pose P = load_pose(T);
-  const int i = (int)(n % nx);
-  const int64_t rest = n / nx;
-  const int j = (int)(rest % ny), k = (int)(rest / ny);
-  const double e0 = (ox + pitch * (double)i) - P.t[0];
-  const double e1 = (oy + pitch * (double)j) - P.t[1];
-  const double e2 = (oz + pitch * (double)k) - P.t[2];
-  const double x = (P.R[0] * e0 + P.R[3] * e1) + P.R[6] * e2;
-  const double y = (P.R[1] * e0 + P.R[4] * e1) + P.R[7] * e2;
-  const double z = (P.R[2] * e0 + P.R[5] * e1) + P.R[8] * e2;
-  if (!(z > 0.0)) return;
-  const double col = floor((fx * (x / z) + cx) + 0.5);
-  const double row = floor((fy * (y / z) + cy) + 0.5);
-  if (!(col >= 0.0 && col <= (double)(W - 1) && row >= 0.0 && row <= (double)(H - 1))) return;
-  const double D = (double)depth[(int64_t)(int)row * W + (int)col];
-  if (!(D > 0.0)) return;
-  const double sdf = D - z;
-  if (!(sdf >= -truncation)) return;
-  double f = sdf / truncation;
-  if (f > 1.0) f = 1.0;
-  const float2 old = vol[n];
-  const double F_old = (double)old.x, W_old = (double)old.y;
-  double w = W_old + 1.0;
-  const double F = (F_old * W_old + f) / w;
-  if (w > max_weight) w = max_weight;
-  vol[n] = make_float2((float)F, (float)w);
+  int64_t pixel;
+  double sdf;
+  mf_tsdf::integrate_voxel(vol, n, nx, ny, ox, oy, oz, pitch, truncation, max_weight, depth, H, W, fx, fy, cx, cy, P,
+                           pixel, sdf);
 }
 
 __global__ void __launch_bounds__(kTile *kTile) k_tsdf_raycast(
