@@ -4,12 +4,14 @@ integrate_tracked_frame (one occupancy map per stable id) -> target grids -> Mod
 object is spawned once three of its poses agree).  Prints the id table of every frame.
 
     python examples/multiview_mapping.py [--frames 3] [--model <chainer .npz checkpoint>]
-                                       [--track-camera | --track-model [--save-mesh PATH]]
+                                       [--track-camera | --track-model [--save-mesh PATH] [--skip-empty]]
 
 --track-camera: the sensor pose is CameraTracker.track(depth) (dense depth alignment, frame to frame, anchored at frame
 0's pose) instead of the sequence's ground truth; its error against the ground truth is printed per frame.
 --track-model: the same through ModelTracker: every frame is aligned to a ray-cast of the TSDF volume that the earlier
 frames were fused into (1 cm voxels over the scene), frame to model instead of frame to frame.
+--skip-empty (with --track-model): ModelTracker takes its reference from TsdfVolume.render, the ray-cast that skips free
+and unseen space through a block summary of the volume (the same bytes, so the same poses).
 --save-mesh PATH (with --track-model): after the last frame the fused model is written as a Wavefront OBJ
 (TsdfVolume.extract_mesh, geometry.save_obj).
 """
@@ -51,11 +53,15 @@ def main():
     ap.add_argument("--track-model", action="store_true",
                     help="estimate the sensor pose by aligning every frame to the fused TSDF model")
     ap.add_argument("--save-mesh", metavar="PATH", help="with --track-model: write the fused model as an OBJ")
+    ap.add_argument("--skip-empty", action="store_true",
+                    help="with --track-model: render the model with empty-space skipping (TsdfVolume.render)")
     args = ap.parse_args()
     if args.track_camera and args.track_model:
         ap.error("--track-camera or --track-model, not both")
     if args.save_mesh and not args.track_model:
         ap.error("--save-mesh needs --track-model")
+    if args.skip_empty and not args.track_model:
+        ap.error("--skip-empty needs --track-model")
     frames = morefusion.synthetic.make_tracking_sequence(0, args.frames)
     models = PitchTableModels()
     pitch_of = lambda c: models.get_voxel_pitch(32, int(c))  # noqa: E731
@@ -85,7 +91,7 @@ def main():
         height, width = frames[0]["depth"].shape
         camera = morefusion.contrib.ModelTracker(frames[0]["K"], height, width,
                                                  morefusion.contrib.TsdfVolume(**MODEL_VOLUME),
-                                                 T_first=frames[0]["T_sensor_to_map"])
+                                                 T_first=frames[0]["T_sensor_to_map"], skip_empty=args.skip_empty)
     for k, f in enumerate(frames):
         K, T = f["K"], f["T_sensor_to_map"]
         if camera is not None:

@@ -8,7 +8,7 @@ before and after the refinement.
 
     python examples/online_pose_refinement.py [--frames 3] [--model <chainer .npz checkpoint>] [--render-service]
                                               [--track-camera | --track-model [--save-mesh PATH]
-                                               [--grids-from-model]]
+                                               [--grids-from-model] [--skip-empty]]
 
 --render-service: the tracker matches against the reference's render-service route (use_render_service,
 OctomapServer.cpp:126-135) -- OctomapServer.grids_in_map_frame meshed and rasterised (contrib.render_voxel_grids) --
@@ -22,6 +22,9 @@ frames were fused into (1 cm voxels over the scene), frame to model instead of f
 tracked labels of every frame next to its depth, and the grids of the pose stage are InstanceTsdfVolume.publish_grids
 (the fused model, the same dict) instead of OctomapServer.publish_grids.  The server is still filled: the instance
 tracker matches its detections against the server's maps.
+--skip-empty (with --track-model): ModelTracker takes its reference from TsdfVolume.render, the ray-cast that skips free
+and unseen space through a block summary of the volume (the same bytes, so the same poses); with --grids-from-model the
+instance ids the fused model shows from the frame's pose are printed too, depth and labels from that one render launch.
 --save-mesh PATH (with --track-model): after the last frame the fused model is written as a Wavefront OBJ
 (TsdfVolume.extract_mesh, geometry.save_obj).
 """
@@ -68,6 +71,8 @@ def main():
     ap.add_argument("--grids-from-model", action="store_true",
                     help="with --track-model: fuse the tracked labels into the TSDF volume and take the pose stage's "
                          "grids from it (InstanceTsdfVolume.publish_grids) instead of from the map server")
+    ap.add_argument("--skip-empty", action="store_true",
+                    help="with --track-model: render the model with empty-space skipping (TsdfVolume.render)")
     args = ap.parse_args()
     if args.track_camera and args.track_model:
         ap.error("--track-camera or --track-model, not both")
@@ -75,6 +80,8 @@ def main():
         ap.error("--save-mesh needs --track-model")
     if args.grids_from_model and not args.track_model:
         ap.error("--grids-from-model needs --track-model")
+    if args.skip_empty and not args.track_model:
+        ap.error("--skip-empty needs --track-model")
     frames = morefusion.synthetic.make_tracking_sequence(0, args.frames)
     models = PitchTableModels()
     pitch_of = lambda c: models.get_voxel_pitch(32, int(c))  # noqa: E731
@@ -107,7 +114,8 @@ def main():
         height, width = frames[0]["depth"].shape
         volume = (morefusion.contrib.InstanceTsdfVolume if args.grids_from_model else morefusion.contrib.TsdfVolume)
         camera = morefusion.contrib.ModelTracker(frames[0]["K"], height, width, volume(**MODEL_VOLUME),
-                                                 T_first=TO_GROUND @ frames[0]["T_sensor_to_map"])
+                                                 T_first=TO_GROUND @ frames[0]["T_sensor_to_map"],
+                                                 skip_empty=args.skip_empty)
     classes = {}  # instance id -> class id, over the frames so far
     for k, f in enumerate(frames):
         K, T = f["K"], TO_GROUND @ f["T_sensor_to_map"]
@@ -138,6 +146,9 @@ def main():
             grids = camera.volume.publish_grids(T, ids, pitch={i: pitch_of(classes[i]) for i in ids}, class_ids=classes,
                                                 ground_z=0.0 if server.ground_as_noentry else None,
                                                 free_as_noentry=server.free_as_noentry)
+            if args.skip_empty:  # depth and labels of the model from one launch
+                _, model_label = camera.volume.render(K, T, height, width, labels=True)
+                print(f"frame {k}: the model's render shows ids {sorted(set(model_label.unique().tolist()) - {0, -1})}")
         else:
             grids = server.publish_grids(T)
         source = "model" if args.grids_from_model else tracker.render

@@ -1584,6 +1584,60 @@ int mf_tsdf_publish_grids(const float *volume, const int32_t *labels, int32_t nx
                           double ground_z, int32_t flags, int32_t B, int32_t D, double *origin, float *grid_target,
                           float *grid_noentry, uint8_t *grid_nontarget_empty, mfStream_t stream);
 
+/* ---- TSDF render: the ray-cast with empty-space skipping and the label image fused in (contrib/tsdf_volume.py,
+ * contrib/instance_tsdf_volume.py, csrc/tsdfrender.hip) ----
+ * TsdfVolume.render / InstanceTsdfVolume.render (DESIGN.md "TSDF render"; tests/tsdfrender_ref.py is the NumPy mirror,
+ * bit for bit, written from this text).  All arrays are DEVICE arrays; every call is asynchronous on `stream`, allocates
+ * nothing and never synchronises.  VOLUME, origin, pitch, POSE and ARITHMETIC are those of "TSDF fusion", LABELS and
+ * INSIDE those of "TSDF labels".
+ *
+ * CELLS AND BLOCKS: cell b = (b_x, b_y, b_z), 0 <= b_a <= n_a - 2, is what floor(g) of a ray sample names; its corners
+ * are the voxels b + {0, 1}^3.  With the block edge B (2, 4, 8 or 16), block (I, J, K) = (I_x, I_y, I_z) holds the cells
+ * b_a in [B I_a, min(B I_a + B - 1, n_a - 2)]: nb_a = ceil((n_a - 1) / B) blocks per axis.  Its FOOTPRINT is the voxels
+ * those cells touch, [B I_a, min(B I_a + B, n_a - 1)] per axis (up to (B + 1)^3; neighbouring blocks share a layer).
+ * SUMMARY: uint8 [nb_z][nb_y][nb_x], x fastest, one code per block:
+ *   FREE     every footprint voxel has weight > 0 and tsdf == 1.0f (compared as values: a NaN is not free)
+ *   UNKNOWN  no footprint voxel has weight > 0 (the negation of > 0: a NaN weight counts as unknown)
+ *   MIXED    anything else
+ * A summary describes the volume it was made from; after an integrate it is stale and must be made again.
+ * Refused with -hipErrorInvalidValue (the function's name in mf_last_error_string; mf_tsdf_summary_bytes returns a
+ * negative value) unless: everything "TSDF fusion" asks of mf_tsdf_raycast's arguments; B is 2, 4, 8 or 16; summary is
+ * non-null; labels and label_out are both null or both non-null, and min_count >= 1 if they are given (code_out and
+ * stats_out may be null). */
+#define MF_TSDF_BLOCK_MIXED 0
+#define MF_TSDF_BLOCK_FREE 1
+#define MF_TSDF_BLOCK_UNKNOWN 2
+/* Host-only: the summary's bytes, nb_x nb_y nb_z; < 0 for a bad volume or B. */
+int64_t mf_tsdf_summary_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t B);
+/* One launch that reads the volume once, plus the layers neighbouring blocks share, and writes the code of EVERY block
+ * (no pre-fill).  A workgroup per (256 voxels along x, J, K), a lane per voxel of the x run; the reduction is a logical
+ * OR of two bits per voxel through wave ballots, so no result depends on an order. */
+int mf_tsdf_block_summary(const float *volume, int32_t nx, int32_t ny, int32_t nz, int32_t B, uint8_t *summary,
+                          mfStream_t stream);
+/* mf_tsdf_raycast of the same arguments with the samples of FREE and UNKNOWN blocks not loaded: depth_out and code_out
+ * are written for EVERY pixel as that contract says, word for word -- the slab test, s = enter + double(k) * step, LEFT
+ * before CAP, g, b, r, F and the hit depth.  Only how a sample's outcome is obtained differs: with b of sample k,
+ *   b in range and its block FREE:     the sample is VALID with F = 1.0 (what 1 + r * (1 - 1) gives on every axis)
+ *   b in range and its block UNKNOWN:  the sample is INVALID
+ *   otherwise (MIXED, or b out of range): as mf_tsdf_raycast evaluates it.
+ * With the summary of this volume these are the outcomes of mf_tsdf_raycast, so the bytes are equal whatever the
+ * volume holds.  The kernel may go from a sample k in a FREE or UNKNOWN block straight to a later sample k' iff sample
+ * k' has its b in the SAME block, enter + double(k') * step <= exit and k' < max_steps: floor(g_a) is monotone in k on
+ * every axis, so every sample between lies in that block too.  After a FREE run previous = 1.0, after an UNKNOWN run
+ * none.  No output depends on how far the kernel tries to go.
+ * label_out int32 [H][W] (with labels, "TSDF labels"): mf_tsdf_label_image's rule applied to the float32 depth_out of
+ * the pixel: d = double(depth_out), unless d > 0: 0, else p = (q_0 * d, q_1 * d, d), m = T_sensor_to_map p, the label of
+ * m's voxel if m is inside and its count >= min_count, else 0.  Written for every pixel.
+ * stats_out int32 [H][W][2] = (sampled, visited).  A ray's samples are the k that passed both tests (LEFT, CAP).
+ * sampled: those of them that were not classified FREE or UNKNOWN (MIXED or out of range), the one that ended the ray
+ * included; fixed by the inputs.  visited: the samples whose position the kernel computed at all; it depends on how the
+ * kernel jumps, and sampled <= visited <= the number of samples. */
+int mf_tsdf_render(const float *volume, int32_t nx, int32_t ny, int32_t nz, double origin_x, double origin_y,
+                   double origin_z, double pitch, double step, double min_depth, double max_depth, int32_t max_steps,
+                   int32_t H, int32_t W, double fx, double fy, double cx, double cy, const double *T_sensor_to_map,
+                   const uint8_t *summary, int32_t B, const int32_t *labels, int32_t min_count, float *depth_out,
+                   uint8_t *code_out, int32_t *label_out, int32_t *stats_out, mfStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -275,6 +275,9 @@ _SIGNATURES = {
     "mf_tsdf_label_image": ([_p] + [_i] * 3 + [_d] * 4 + [_p, _i, _i] + [_d] * 4 + [_p, _i, _p, _p], _i),
     "mf_tsdf_instance_stats": ([_p, _p] + [_i] * 3 + [_d, _i, _p, _i, _p, _p], _i),
     "mf_tsdf_publish_grids": ([_p, _p] + [_i] * 3 + [_d] * 4 + [_p] * 5 + [_d, _i, _d, _d] + [_i] * 3 + [_p] * 5, _i),
+    "mf_tsdf_summary_bytes": ([_i] * 4, _i64),
+    "mf_tsdf_block_summary": ([_p] + [_i] * 4 + [_p, _p], _i),
+    "mf_tsdf_render": ([_p] + [_i] * 3 + [_d] * 7 + [_i] * 3 + [_d] * 4 + [_p, _p, _i, _p, _i] + [_p] * 5, _i),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

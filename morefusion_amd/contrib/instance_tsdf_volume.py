@@ -108,6 +108,19 @@ class InstanceTsdfVolume(TsdfVolume):
             fx, fy, cx, cy, _lib.ptr(T), min_count, _lib.ptr(out), _lib.stream_ptr()), "mf_tsdf_label_image")
         return out
 
+    def render(self, K, T_sensor_to_map, height, width, step=None, min_depth=0.0, max_depth=None, block=8,
+               summary=None, return_code=False, return_stats=False, labels=False, min_count=1):
+        """``TsdfVolume.render``; with ``labels`` the same launch also gives the int32 [height, width] label image,
+        the bytes of ``label_image(depth, K, T_sensor_to_map, min_count)`` on the depth it returns.
+        -> depth, then the label image, code and stats, each if asked for."""
+        min_count = _count(min_count, "min_count")
+        depth, label, code, stats = self._render(K, T_sensor_to_map, height, width, step, min_depth, max_depth, block,
+                                                 summary, self.labels if labels else None, min_count, return_code,
+                                                 return_stats)
+        out = (depth,) + ((label,) if labels else ()) + ((code,) if return_code else ()) + \
+            ((stats,) if return_stats else ())
+        return out if len(out) > 1 else depth
+
     @staticmethod
     def _ids(ids):
         ids = [int(i) for i in ids]

@@ -23,6 +23,8 @@ from .camera_tracking import CameraTracker, _depth_tensor, _intrinsics, _pose_te
 
 MAX_STEPS = 65536  # MF_TSDF_MAX_STEPS (include/mfhip.h)
 RAY_HIT, RAY_LEFT, RAY_BACKFACE, RAY_MISS, RAY_CAP = range(5)  # MF_TSDF_RAY_*
+BLOCK_MIXED, BLOCK_FREE, BLOCK_UNKNOWN = range(3)  # MF_TSDF_BLOCK_*
+BLOCK_EDGES = (2, 4, 8, 16)
 
 
 def _camera(K):
@@ -113,7 +115,22 @@ class TsdfVolume:
         ``step`` metres of depth (default ``truncation / 2``) between ``min_depth`` and ``max_depth`` (default: no
         limit) inside the volume and the zero crossing is interpolated between the two samples around it.  With
         ``return_code`` also a uint8 image of how each ray ended (``RAY_HIT`` .. ``RAY_CAP``)."""
-        fx, fy, cx, cy = _camera(K)
+        camera, (height, width), (step, min_depth, max_depth, max_steps) = self._ray_arguments(
+            K, height, width, step, min_depth, max_depth)
+        T = self._pose(T_sensor_to_map)
+        depth = torch.empty((height, width), dtype=torch.float32, device=self.device)
+        code = torch.empty((height, width), dtype=torch.uint8, device=self.device) if return_code else None
+        _lib.require_gpu(self.volume, T, depth)
+        _lib.check(_lib.lib().mf_tsdf_raycast(
+            _lib.ptr(self.volume), *self.dims, *self.origin, self.pitch, step, min_depth, max_depth, max_steps,
+            height, width, *camera, _lib.ptr(T), _lib.ptr(depth), _lib.ptr(code), _lib.stream_ptr()),
+            "mf_tsdf_raycast")
+        return (depth, code) if return_code else depth
+
+    def _ray_arguments(self, K, height, width, step, min_depth, max_depth):
+        """The checks and defaults that ``raycast`` and ``render`` share -> ((fx, fy, cx, cy), (height, width), (step,
+        min_depth, max_depth, max_steps))."""
+        camera = _camera(K)
         height, width = int(height), int(width)
         if height < 1 or width < 1:
             raise ValueError(f"height x width = {height} x {width}: each >= 1")
@@ -127,15 +144,66 @@ class TsdfVolume:
         max_steps = self.max_steps(step)
         if max_steps > MAX_STEPS:
             raise ValueError(f"step = {step}: {max_steps} samples per ray, at most {MAX_STEPS}")
+        return camera, (height, width), (step, min_depth, max_depth, max_steps)
+
+    def summary_shape(self, block=8):
+        """(nb_z, nb_y, nb_x) of ``block_summary``: ``ceil((n - 1) / block)`` blocks of cells per axis."""
+        block = int(block)
+        if block not in BLOCK_EDGES:
+            raise ValueError(f"block = {block}: one of {BLOCK_EDGES}")
+        nx, ny, nz = self.dims
+        return tuple((n - 2) // block + 1 for n in (nz, ny, nx))
+
+    def block_summary(self, block=8):
+        """The coarse occupancy that ``render`` skips with: a uint8 device tensor ``[nb_z, nb_y, nb_x]`` with one code
+        per block of ``block``^3 cells (2, 4, 8 or 16) -- ``BLOCK_FREE`` if every voxel the block's cells touch was
+        seen (weight > 0) with tsdf exactly 1, ``BLOCK_UNKNOWN`` if none of them was seen, ``BLOCK_MIXED`` otherwise.
+        One launch that reads the volume once.  It describes the volume as it is now: any integrate makes it stale."""
+        summary = torch.empty(self.summary_shape(block), dtype=torch.uint8, device=self.device)
+        _lib.require_gpu(self.volume, summary)
+        _lib.check(_lib.lib().mf_tsdf_block_summary(_lib.ptr(self.volume), *self.dims, int(block), _lib.ptr(summary),
+                                                    _lib.stream_ptr()), "mf_tsdf_block_summary")
+        return summary
+
+    def _render(self, K, T_sensor_to_map, height, width, step, min_depth, max_depth, block, summary, labels, min_count,
+                want_code, want_stats):
+        """-> (depth, label or None, code or None, stats or None) of one ``mf_tsdf_render`` launch."""
+        camera, (height, width), (step, min_depth, max_depth, max_steps) = self._ray_arguments(
+            K, height, width, step, min_depth, max_depth)
+        shape = self.summary_shape(block)
+        if summary is None:
+            summary = self.block_summary(block)
+        elif (not isinstance(summary, torch.Tensor) or summary.dtype != torch.uint8 or tuple(summary.shape) != shape
+              or not summary.is_contiguous()):
+            raise ValueError(f"summary must be a contiguous uint8 tensor {shape}: block_summary({int(block)})")
+        elif summary.device != self.volume.device:
+            raise ValueError(f"summary on {summary.device}, the volume on {self.volume.device}")
         T = self._pose(T_sensor_to_map)
-        depth = torch.empty((height, width), dtype=torch.float32, device=self.device)
-        code = torch.empty((height, width), dtype=torch.uint8, device=self.device) if return_code else None
-        _lib.require_gpu(self.volume, T, depth)
-        _lib.check(_lib.lib().mf_tsdf_raycast(
+        new = lambda dtype, *tail: torch.empty((height, width) + tail, dtype=dtype, device=self.device)  # noqa: E731
+        depth = new(torch.float32)
+        label = None if labels is None else new(torch.int32)
+        code = new(torch.uint8) if want_code else None
+        stats = new(torch.int32, 2) if want_stats else None
+        _lib.require_gpu(self.volume, summary, T, depth, *(() if labels is None else (labels,)))
+        _lib.check(_lib.lib().mf_tsdf_render(
             _lib.ptr(self.volume), *self.dims, *self.origin, self.pitch, step, min_depth, max_depth, max_steps,
-            height, width, fx, fy, cx, cy, _lib.ptr(T), _lib.ptr(depth), _lib.ptr(code), _lib.stream_ptr()),
-            "mf_tsdf_raycast")
-        return (depth, code) if return_code else depth
+            height, width, *camera, _lib.ptr(T), _lib.ptr(summary), int(block), _lib.ptr(labels), int(min_count),
+            _lib.ptr(depth), _lib.ptr(code), _lib.ptr(label), _lib.ptr(stats), _lib.stream_ptr()), "mf_tsdf_render")
+        return depth, label, code, stats
+
+    def render(self, K, T_sensor_to_map, height, width, step=None, min_depth=0.0, max_depth=None, block=8,
+               summary=None, return_code=False, return_stats=False):
+        """``raycast`` (same arguments, same checks, the same bytes in depth and code) without the loads that free and
+        unseen space cost: a sample inside a ``BLOCK_FREE`` or ``BLOCK_UNKNOWN`` block of ``block_summary(block)`` reads
+        one byte of the summary, and the ray goes to its last sample inside such a block in one step (csrc/tsdfrender.hip,
+        include/mfhip.h "TSDF render").  The summary is made again on every call -- one read of the volume -- unless
+        ``summary`` is given; a summary made before the last integrate is stale and gives a wrong render: passing one is
+        the caller's risk.  ``return_stats``: also an int32 ``[height, width, 2]`` tensor of (samples evaluated by
+        loading voxels, samples whose position was computed) per ray.  -> depth, then code and stats if asked for."""
+        depth, _, code, stats = self._render(K, T_sensor_to_map, height, width, step, min_depth, max_depth, block,
+                                             summary, None, 1, return_code, return_stats)
+        out = (depth,) + ((code,) if return_code else ()) + ((stats,) if return_stats else ())
+        return out if len(out) > 1 else depth
 
     def extract_mesh(self, min_weight=1.0, normals=False):
         """The fused surface as a welded triangle mesh (csrc/tsdfmesh.hip, include/mfhip.h "TSDF mesh"): ``(vertices
@@ -182,12 +250,16 @@ class ModelTracker:
     the last one (``CameraTracker`` restores the initial pose).  Nothing is read back in the loop.
     ``track(depth, label)`` also fuses the frame's instance labels; ``volume`` must then be an ``InstanceTsdfVolume``.
     ``tracker_kwargs`` go to ``CameraTracker`` (levels, iterations, block_band, the thresholds, min_pairs).
+    ``skip_empty``: the reference comes from ``volume.render(..., block=block)`` -- the same bytes as the ray-cast's,
+    so the same poses and the same model; the summary is made again for every frame, on the device.
 
     ``status`` / ``lost`` / ``stats`` are the inner tracker's, read back only when asked for."""
 
-    def __init__(self, K, height, width, volume, T_first=None, **tracker_kwargs):
+    def __init__(self, K, height, width, volume, T_first=None, skip_empty=False, block=8, **tracker_kwargs):
         if not isinstance(volume, TsdfVolume):
             raise TypeError(f"volume must be a TsdfVolume, got {type(volume).__name__}")
+        self.skip_empty, self.block = bool(skip_empty), int(block)
+        volume.summary_shape(self.block)  # (refuses a block edge that is not allowed)
         for name in ("reference", "device"):
             if name in tracker_kwargs:
                 raise TypeError(f"{name} is fixed by ModelTracker: the reference is the model, the device the volume's")
@@ -211,7 +283,10 @@ class ModelTracker:
             self.volume.integrate(d, self.K, self._T_first, **labelled(self._T_first))
             self._T_last = self._T_first
             return self._T_last.clone()
-        reference = self.volume.raycast(self.K, self._T_last, self.height, self.width)
+        if self.skip_empty:
+            reference = self.volume.render(self.K, self._T_last, self.height, self.width, block=self.block)
+        else:
+            reference = self.volume.raycast(self.K, self._T_last, self.height, self.width)
         self.tracker.set_reference(reference, self._T_last)
         T = self.tracker.track(d, T_init=self._T_last)
         # (the device word: no read-back)
