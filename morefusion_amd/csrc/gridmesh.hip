@@ -5,15 +5,11 @@
 // 0.5-level set of the occupancy over the six-tetrahedra (Kuhn) subdivision of the padded lattice (DESIGN.md "Grid
 // meshes": trimesh / scikit-image parity unpinned).
 //
-// Lattice: grid b of X x Y x Z cells padded by one empty layer, P = (X + 2, Y + 2, Z + 2) points.  A point owns the
-// seven edges towards +(1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1); an edge whose ends differ in occupancy
-// is a vertex, numbered by its rank in (x, y, z, direction) order.  Tetrahedron t of a cell walks the axes
-// kAxes[t] = xyz, xzy, yxz, yzx, zxy, zyx: corners c0 = cell, c1 = c0 + e_a, c2 = c1 + e_b, c3 = cell + (1,1,1).
-// With the mask m (bit i: corner i occupied) and e(i,j) the vertex on the edge between corners i and j:
-//   one corner i alone on its side:  (e(i,j0), e(i,j1), e(i,j2)), j ascending;
-//   corners a < b occupied, c < d empty:  (e(a,c), e(a,d), e(b,d)) then (e(a,c), e(b,d), e(b,c));
-// the last two vertices of a triangle are exchanged where that makes it counter-clockwise seen from the empty side
-// (kFlip for an even walk, inverted for an odd one).  Faces are numbered in (cell x, y, z, tetrahedron, triangle) order.
+// Lattice: grid b of X x Y x Z cells padded by one empty layer, P = (X + 2, Y + 2, Z + 2) points.  An edge of the
+// subdivision whose ends differ in occupancy is a vertex, numbered by its rank in (x, y, z, direction) order; faces are
+// numbered in (cell x, y, z, tetrahedron, triangle) order.  The subdivision itself -- corner codes, the edges a point
+// owns, which faces a cell has and how they wind -- is kuhn_mesh.h's, shared with csrc/tsdfmesh.hip; the workgroup scan
+// is block_scan.h's.
 //
 // Launches: k_gm_count (grid, x-slab) -> k_gm_scan -> [host reads the offsets] -> k_gm_emit (grid, x-slab);
 // k_gm_adj_fill / k_gm_adj_sort build each vertex's neighbour row (at most 12: an edge of the subdivision lies in at
@@ -22,6 +18,9 @@
 #include <limits.h>
 #include <math.h>
 
+#include "block_scan.h"
+#include "host_args.h"
+#include "kuhn_mesh.h"
 #include "mf_common.h"
 
 namespace {
@@ -31,13 +30,6 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kPad = MF_GRIDMESH_MAX_DIM + 2;  // 34 lattice points per axis at most
 constexpr int kLayer = kPad * kPad;            // points of one x-layer
 constexpr int kNbr = MF_GRIDMESH_MAX_NEIGHBOURS;
-
-// corner codes are dx * 4 + dy * 2 + dz
-__device__ const unsigned char kCorner[6][4] = {{0, 4, 6, 7}, {0, 4, 5, 7}, {0, 2, 6, 7},
-                                                {0, 2, 3, 7}, {0, 1, 5, 7}, {0, 1, 3, 7}};
-__device__ const unsigned char kOdd[6] = {0, 1, 1, 0, 0, 1};             // parity of the walk
-__device__ const signed char kDirOfCode[8] = {-1, 2, 1, 5, 0, 4, 3, 6};  // edge direction of a corner-code difference
-constexpr unsigned kFlip = 0x4D24u;  // masks 2, 5, 8, 10, 11, 14 of an even walk
 
 struct Grid {
   int X, Y, Z, Px, Py, Pz;
@@ -97,49 +89,6 @@ __device__ __forceinline__ unsigned cell_corners(const unsigned char (*s_occ)[kL
   return c;
 }
 
-__device__ __forceinline__ unsigned tet_mask(unsigned corners, int t) {
-  unsigned m = 0;
-  for (int i = 0; i < 4; ++i) m |= ((corners >> kCorner[t][i]) & 1u) << i;
-  return m;
-}
-
-__device__ __forceinline__ int faces_of_mask(unsigned m) {
-  const int pc = __popc(m);
-  return pc == 2 ? 2 : (pc & 1);
-}
-
-__device__ __forceinline__ int cell_faces(unsigned corners) {
-  if (corners == 0u || corners == 255u) return 0;
-  int n = 0;
-  for (int t = 0; t < 6; ++t) n += faces_of_mask(tet_mask(corners, t));
-  return n;
-}
-
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = threadIdx.x & 63;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int u = __shfl_up(v, d);
-    if (lane >= d) v += u;
-  }
-  return v;
-}
-
-// exclusive prefix of v over the workgroup's threads and the total; every thread calls it
-__device__ __forceinline__ int block_excl_scan(int v, int *s_w, int &total) {
-  const int inc = wave_incl_scan(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();  // the previous call's s_w has been read
-  if ((threadIdx.x & 63) == 63) s_w[w] = inc;
-  __syncthreads();
-  int base = 0;
-  total = 0;
-  for (int i = 0; i < kWaves; ++i) {
-    if (i < w) base += s_w[i];
-    total += s_w[i];
-  }
-  return base + inc - v;
-}
-
 // counts[b][px] = vertices of the layer's points | faces of the layer's cells << 16
 __global__ __launch_bounds__(kThreads) void k_gm_count(const float *__restrict__ grids, const int64_t *__restrict__ g_off,
                                                        const int32_t *__restrict__ dims, int32_t *__restrict__ counts) {
@@ -161,7 +110,7 @@ __global__ __launch_bounds__(kThreads) void k_gm_count(const float *__restrict__
     if (cells && y < g.Py - 1 && z < g.Pz - 1) packed += cell_faces(cell_corners(s_occ, g, y, z)) << 16;
   }
   int total;
-  block_excl_scan(packed, s_w, total);  // a layer has at most 8092 vertices and 13872 faces: no carry between the halves
+  block_excl_scan<kWaves>(packed, s_w, total);  // a layer has at most 8092 vertices and 13872 faces: no carry between the halves
   if (threadIdx.x == 0) counts[b * kPad + px] = total;
 }
 
@@ -222,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void k_gm_emit(const float *__restrict__ 
       unsigned m = 0;
       if (i < n) m = point_mask(s_occ, g, L, i / g.Pz, i % g.Pz);
       int total;
-      const int excl = block_excl_scan(__popc(m), s_w, total);
+      const int excl = block_excl_scan<kWaves>((int)__popc(m), s_w, total);
       if (i < n) {
         s_mask[L][i] = (unsigned char)m;
         s_vbase[L][i] = running + excl;
@@ -241,7 +190,7 @@ __global__ __launch_bounds__(kThreads) void k_gm_emit(const float *__restrict__ 
     int64_t at = v0 + s_vbase[0][i];
     for (int d = 0; d < 7; ++d) {
       if (!((m >> d) & 1u)) continue;
-      const int code = d == 0 ? 4 : d == 1 ? 2 : d == 2 ? 1 : d == 3 ? 6 : d == 4 ? 5 : d == 5 ? 3 : 7;
+      const int code = code_of_dir(d);
       const int e[3] = {(code >> 2) & 1, (code >> 1) & 1, code & 1};
       if (at >= v0 && at < v_end)
         for (int a = 0; a < 3; ++a) vertices[3 * at + a] = o[a] + h * ((double)(2 * p[a] + e[a]) / 2.0 - 1.0);
@@ -256,47 +205,13 @@ __global__ __launch_bounds__(kThreads) void k_gm_emit(const float *__restrict__ 
     const int y = i / cz_n, z = i % cz_n;
     const unsigned corners = i < nc ? cell_corners(s_occ, g, y, z) : 0u;
     int total;
-    int64_t at = f0 + running + block_excl_scan(cell_faces(corners), s_w, total);
+    const int64_t at = f0 + running + block_excl_scan<kWaves>(cell_faces(corners), s_w, total);
     running += total;
-    if (corners == 0u || corners == 255u) continue;
-    for (int t = 0; t < 6; ++t) {
-      const unsigned m = tet_mask(corners, t);
-      const int pc = __popc(m);
-      if (pc == 0 || pc == 4) continue;
-      // e(i, j): the vertex on the edge between corners i < j of this tetrahedron
-      auto edge = [&](int ci, int cj) {
-        const int lo = kCorner[t][ci < cj ? ci : cj], hi = kCorner[t][ci < cj ? cj : ci];
-        const int d = kDirOfCode[hi - lo];  // the walk only adds axes: hi - lo is the code of the difference
-        const int pi = (y + ((lo >> 1) & 1)) * g.Pz + z + (lo & 1), L = lo >> 2;
-        return s_vbase[L][pi] + __popc((unsigned)s_mask[L][pi] & ((1u << d) - 1u));
-      };
-      const bool flip = (((kFlip >> m) & 1u) != 0u) != (kOdd[t] != 0);
-      int tri[2][3];
-      if (pc == 2) {
-        int in[2], out[2], ni = 0, no = 0;
-        for (int k = 0; k < 4; ++k) {
-          if ((m >> k) & 1u) in[ni++] = k;
-          else out[no++] = k;
-        }
-        const int ac = edge(in[0], out[0]), ad = edge(in[0], out[1]), bd = edge(in[1], out[1]), bc = edge(in[1], out[0]);
-        tri[0][0] = ac, tri[0][1] = ad, tri[0][2] = bd;
-        tri[1][0] = ac, tri[1][1] = bd, tri[1][2] = bc;
-      } else {
-        const unsigned lone = pc == 1 ? m : (~m & 15u);
-        const int k = __ffs((int)lone) - 1;
-        int j = 0;
-        for (int c = 0; c < 4; ++c)
-          if (c != k) tri[0][j++] = edge(k, c);
-      }
-      for (int q = 0; q < (pc == 2 ? 2 : 1); ++q) {
-        if (at >= f0 && at < f_end) {
-          faces[3 * at] = tri[q][0];
-          faces[3 * at + 1] = tri[q][flip ? 2 : 1];
-          faces[3 * at + 2] = tri[q][flip ? 1 : 2];
-        }
-        ++at;
-      }
-    }
+    const auto vertex_of = [&](int lo, int d) {
+      const int pi = (y + ((lo >> 1) & 1)) * g.Pz + z + (lo & 1), L = lo >> 2;  // the owner's point and layer
+      return s_vbase[L][pi] + __popc((unsigned)s_mask[L][pi] & ((1u << d) - 1u));
+    };
+    emit_cell_faces(corners, at, f0, f_end, faces, vertex_of);
   }
 }
 
@@ -417,13 +332,6 @@ __global__ __launch_bounds__(kThreads) void k_gm_label(const float *__restrict__
   }
   label[i] = l;
 }
-
-int bad(const char *what) {
-  mf::set_last_error(hipErrorInvalidValue, what);
-  return -(int)hipErrorInvalidValue;
-}
-
-int64_t align16(int64_t n) { return (n + 15) & ~(int64_t)15; }
 
 int64_t count_bytes(int64_t B) { return align16(B * kPad * 4) + align16(B * kPad * 2 * 4); }
 

@@ -1,5 +1,9 @@
-// The voxel body of TSDF integration (include/mfhip.h "TSDF fusion"), shared by k_tsdf_integrate (csrc/tsdf.hip) and
-// k_tsdf_integrate_labels (csrc/tsdflabel.hip): one text, so the (tsdf, weight) bytes of the two kernels cannot differ.
+// What the TSDF kernels say about one voxel, one text each so that the bytes of two kernels cannot differ:
+//   integrate_voxel  the voxel body of TSDF integration (include/mfhip.h "TSDF fusion"): k_tsdf_integrate
+//                    (csrc/tsdf.hip) and k_tsdf_integrate_labels (csrc/tsdflabel.hip) store the same (tsdf, weight);
+//   voxel_of         the voxel a map point falls into ("TSDF labels"): k_tsdf_label_image, k_tsdf_publish_grids
+//                    (csrc/tsdflabel.hip) and, through label_at, k_tsdf_render (csrc/tsdfrender.hip);
+//   label_at         the label of the voxel a depth pixel falls into: k_tsdf_label_image and k_tsdf_render's label_out.
 // float64, + - * / and floor only, every expression associated as the header writes it; nothing is contracted.
 #pragma once
 #include <math.h>
@@ -57,6 +61,33 @@ __device__ __forceinline__ bool integrate_voxel(float2 *__restrict__ vol, int64_
   if (w > max_weight) w = max_weight;
   vol[n] = make_float2((float)F, (float)w);
   return true;
+}
+
+// floor((m - o) / pitch + 0.5) per axis -> the flat voxel index, or -1 outside the volume (or for a NaN)
+__device__ __forceinline__ int64_t voxel_of(const double (&m)[3], double ox, double oy, double oz, double pitch, int nx,
+                                            int ny, int nz) {
+  const double g0 = floor((m[0] - ox) / pitch + 0.5);
+  const double g1 = floor((m[1] - oy) / pitch + 0.5);
+  const double g2 = floor((m[2] - oz) / pitch + 0.5);
+  if (!(g0 >= 0.0 && g0 <= (double)(nx - 1) && g1 >= 0.0 && g1 <= (double)(ny - 1) && g2 >= 0.0 &&
+        g2 <= (double)(nz - 1)))
+    return -1;
+  return ((int64_t)(int)g2 * ny + (int)g1) * nx + (int)g0;
+}
+
+// The label of the voxel that the pixel of camera ray (q0, q1, 1) falls into at depth d > 0 (the caller's test: a pixel
+// without a depth has label 0): 0 outside the volume and where the voxel's count is below min_count.
+__device__ __forceinline__ int label_at(const int2 *__restrict__ labels, int nx, int ny, int nz, double ox, double oy,
+                                        double oz, double pitch, double q0, double q1, double d, const Pose &P,
+                                        int min_count) {
+  const double x = q0 * d, y = q1 * d;
+  double m[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) m[a] = ((P.R[3 * a] * x + P.R[3 * a + 1] * y) + P.R[3 * a + 2] * d) + P.t[a];
+  const int64_t n = voxel_of(m, ox, oy, oz, pitch, nx, ny, nz);
+  if (n < 0) return 0;
+  const int2 lc = labels[n];
+  return lc.y >= min_count ? lc.x : 0;
 }
 
 }  // namespace mf_tsdf

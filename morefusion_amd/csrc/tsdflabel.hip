@@ -7,17 +7,20 @@
 //   k_tsdf_integrate_labels  a lane per voxel, x fastest: the voxel body of k_tsdf_integrate (tsdf_voxel.h, the same
 //                            text: the (tsdf, weight) bytes are those of mf_tsdf_integrate), then one vote on the
 //                            voxel's own (label, count) pair.  A lane reads and writes only its own voxel.
-//   k_tsdf_label_image       a lane per pixel in 16 x 16 tiles: the label of the voxel a depth pixel falls into.
+//   k_tsdf_label_image       a lane per pixel in 16 x 16 tiles: the label of the voxel a depth pixel falls into
+//                            (tsdf_voxel.h's label_at, the same text as the label tail of k_tsdf_render).
 //   k_tsdf_stats_init / k_tsdf_instance_stats
 //                            a lane per voxel; the id list and a [B, 10] int64 table live in LDS, lanes add to it with
 //                            integer LDS atomics and the workgroup adds its non-empty rows to the int64 table in
 //                            memory with 64-bit integer atomics.  Integers only: the result has no order.
-//   k_tsdf_publish_grids     a lane per voxel of all B grids: D^3 samples in the SENSOR frame, looked up in the volume.
+//   k_tsdf_publish_grids     a lane per voxel of all B grids: D^3 samples in the SENSOR frame, looked up in the volume
+//                            (tsdf_voxel.h's voxel_of).
 //
 // No float atomics.  Coordinates use only + - * / and floor, nothing is contracted (-ffp-contract=off).
 #include <limits.h>
 #include <math.h>
 
+#include "host_args.h"
 #include "mf_common.h"
 #include "tsdf_voxel.h"
 
@@ -59,18 +62,6 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_integrate_labels(
   labels[n] = lc;
 }
 
-// floor((m - o) / pitch + 0.5) per axis -> the flat voxel index, or -1 outside the volume (or for a NaN)
-__device__ __forceinline__ int64_t voxel_of(const double (&m)[3], double ox, double oy, double oz, double pitch, int nx,
-                                            int ny, int nz) {
-  const double g0 = floor((m[0] - ox) / pitch + 0.5);
-  const double g1 = floor((m[1] - oy) / pitch + 0.5);
-  const double g2 = floor((m[2] - oz) / pitch + 0.5);
-  if (!(g0 >= 0.0 && g0 <= (double)(nx - 1) && g1 >= 0.0 && g1 <= (double)(ny - 1) && g2 >= 0.0 &&
-        g2 <= (double)(nz - 1)))
-    return -1;
-  return ((int64_t)(int)g2 * ny + (int)g1) * nx + (int)g0;
-}
-
 __global__ void __launch_bounds__(kTile *kTile) k_tsdf_label_image(
     const int2 *__restrict__ labels, int nx, int ny, int nz, double ox, double oy, double oz, double pitch,
     const float *__restrict__ depth, int H, int W, double fx, double fy, double cx, double cy,
@@ -83,15 +74,7 @@ __global__ void __launch_bounds__(kTile *kTile) k_tsdf_label_image(
   if (d > 0.0) {
     const Pose P = load_pose(T);
     const double q0 = ((double)col - cx) / fx, q1 = ((double)row - cy) / fy;
-    const double x = q0 * d, y = q1 * d;
-    double m[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) m[a] = ((P.R[3 * a] * x + P.R[3 * a + 1] * y) + P.R[3 * a + 2] * d) + P.t[a];
-    const int64_t n = voxel_of(m, ox, oy, oz, pitch, nx, ny, nz);
-    if (n >= 0) {
-      const int2 lc = labels[n];
-      if (lc.y >= min_count) label = lc.x;
-    }
+    label = mf_tsdf::label_at(labels, nx, ny, nz, ox, oy, oz, pitch, q0, q1, d, P, min_count);
   }
   out[p] = label;
 }
@@ -184,7 +167,7 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_publish_grids(
   if ((flags & 1) && m[2] < ground_z) {
     ne = 1.0f;  // below the ground plane
   } else {
-    const int64_t n = voxel_of(m, ox, oy, oz, pitch, nx, ny, nz);
+    const int64_t n = mf_tsdf::voxel_of(m, ox, oy, oz, pitch, nx, ny, nz);
     if (n >= 0) {
       const float2 fw = vol[n];
       if ((double)fw.y >= min_weight) {
@@ -203,19 +186,6 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_publish_grids(
   grid_target[g] = gt;
   grid_noentry[g] = ne;
   grid_nte[g] = ne != 0.0f;
-}
-
-int bad(const char *what) {
-  mf::set_last_error(hipErrorInvalidValue, what);
-  return -(int)hipErrorInvalidValue;
-}
-
-bool bad_volume(int32_t nx, int32_t ny, int32_t nz) {
-  return nx < 2 || ny < 2 || nz < 2 || (int64_t)nx * ny * nz >= ((int64_t)1 << 31);
-}
-
-bool bad_camera(int32_t H, int32_t W, double fx, double fy) {
-  return H < 1 || W < 1 || H > MF_RENDER_MAX_SIDE || W > MF_RENDER_MAX_SIDE || !(fx > 0.0) || !(fy > 0.0);
 }
 
 }  // namespace

@@ -2,9 +2,10 @@
 //
 // include/mfhip.h "TSDF mesh" is the contract -- inside / observed, the vertex and face orders, every formula and its
 // association -- and tests/tsdfmesh_ref.py the NumPy mirror this file is pinned to bit for bit; DESIGN.md "TSDF mesh"
-// has the cost model.  The triangulation is the six-tetrahedra subdivision of csrc/gridmesh.hip (its three tables are
-// copied below); what differs is the lattice: a volume far larger than LDS, x fastest, vertices interpolated along
-// their edges, and cells the camera never saw left out.
+// has the cost model.  The triangulation is the six-tetrahedra subdivision of csrc/gridmesh.hip: its tables, face
+// count and face emitter are kuhn_mesh.h's, one text for both files, and the workgroup scan is block_scan.h's.  What
+// differs is the lattice: a volume far larger than LDS, x fastest, vertices interpolated along their edges, and cells
+// the camera never saw left out.
 //
 //   k_tm_flags  a lane per 4 lattice points: the volume is read once, 32 contiguous bytes per lane, and leaves one
 //               byte per point (bit 0 inside, bit 1 observed).  Everything below reads bytes, not the volume.
@@ -22,6 +23,9 @@
 // Integer sums only (no atomics at all), float64 arithmetic on widened float32, nothing contracted.
 #include <math.h>
 
+#include "block_scan.h"
+#include "host_args.h"
+#include "kuhn_mesh.h"
 #include "mf_common.h"
 
 namespace {
@@ -29,13 +33,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kScanThreads = 1024;
-
-// corner codes are dx * 4 + dy * 2 + dz (csrc/gridmesh.hip)
-__device__ const unsigned char kCorner[6][4] = {{0, 4, 6, 7}, {0, 4, 5, 7}, {0, 2, 6, 7},
-                                                {0, 2, 3, 7}, {0, 1, 5, 7}, {0, 1, 3, 7}};
-__device__ const unsigned char kOdd[6] = {0, 1, 1, 0, 0, 1};             // parity of the walk
-__device__ const signed char kDirOfCode[8] = {-1, 2, 1, 5, 0, 4, 3, 6};  // edge direction of a corner-code difference
-constexpr unsigned kFlip = 0x4D24u;  // masks 2, 5, 8, 10, 11, 14 of an even walk
 
 constexpr unsigned kInside = 1u, kObserved = 2u;
 
@@ -54,33 +51,6 @@ __global__ __launch_bounds__(kThreads) void k_tm_flags(const float *__restrict__
   } else {
     for (int64_t m = q; m < n; ++m) flags[m] = (uint8_t)flag_of(vol[2 * m], vol[2 * m + 1], min_weight);
   }
-}
-
-template <class T>
-__device__ __forceinline__ T wave_incl_scan(T v) {
-  const int lane = threadIdx.x & 63;
-  for (int d = 1; d < 64; d <<= 1) {
-    const T u = __shfl_up(v, d);
-    if (lane >= d) v += u;
-  }
-  return v;
-}
-
-// exclusive prefix of v over the workgroup's NW waves and the total; every thread calls it
-template <int NW, class T>
-__device__ __forceinline__ T block_excl_scan(T v, T *s_w, T &total) {
-  const T inc = wave_incl_scan(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();  // the previous call's s_w has been read
-  if ((threadIdx.x & 63) == 63) s_w[w] = inc;
-  __syncthreads();
-  T base = 0;
-  total = 0;
-  for (int i = 0; i < NW; ++i) {
-    if (i < w) base += s_w[i];
-    total += s_w[i];
-  }
-  return base + inc - v;
 }
 
 // Column x of the rows around (k, j), folded into a byte.  Bit (cz + 1) * 2 + (cy + 1), cz, cy in {-1, 0}: the four
@@ -134,22 +104,6 @@ __device__ __forceinline__ unsigned cell_corners(unsigned in0, unsigned in1) {
     c |= ((col >> ((code & 1) * 2 + ((code >> 1) & 1))) & 1u) << code;
   }
   return c;
-}
-
-__device__ __forceinline__ unsigned tet_mask(unsigned corners, int t) {
-  unsigned m = 0;
-  for (int i = 0; i < 4; ++i) m |= ((corners >> kCorner[t][i]) & 1u) << i;
-  return m;
-}
-
-__device__ __forceinline__ int cell_faces(unsigned corners) {
-  if (corners == 0u || corners == 255u) return 0;
-  int n = 0;
-  for (int t = 0; t < 6; ++t) {
-    const int pc = __popc(tet_mask(corners, t));
-    n += pc == 2 ? 2 : (pc & 1);
-  }
-  return n;
 }
 
 // masks[k][j][i] and rows[row] = (vertices, faces) of row = k ny + j
@@ -326,7 +280,7 @@ __global__ __launch_bounds__(kThreads) void k_tm_emit(
       int64_t at = s_vbase[0][tid];
       for (int d = 0; d < 7; ++d) {
         if (!((own[0] >> d) & 1u)) continue;
-        const int code = d == 0 ? 4 : d == 1 ? 2 : d == 2 ? 1 : d == 3 ? 6 : d == 4 ? 5 : d == 5 ? 3 : 7;
+        const int code = code_of_dir(d);
         const int e[3] = {(code >> 2) & 1, (code >> 1) & 1, code & 1};
         if (at >= 0 && at < n_vertices) {
           const double Fb = (double)vol[at_a + ((int64_t)e[2] * ny + e[1]) * nx + e[0]].x;
@@ -349,66 +303,17 @@ __global__ __launch_bounds__(kThreads) void k_tm_emit(
       }
     }
     // the faces of this row's cells
-    if (corners != 0u && corners != 255u) {
-      int64_t at = running_f + (int64_t)((excl >> (4 * kField)) & kFieldMask);
-      for (int t = 0; t < 6; ++t) {
-        const unsigned m = tet_mask(corners, t);
-        const int pc = __popc(m);
-        if (pc == 0 || pc == 4) continue;
-        // e(ci, cj): the vertex on the edge between corners ci, cj of this tetrahedron
-        auto edge = [&](int ci, int cj) {
-          const int lo = kCorner[t][ci < cj ? ci : cj], hi = kCorner[t][ci < cj ? cj : ci];
-          const int d = kDirOfCode[hi - lo];  // the walk only adds axes: hi - lo is the code of the difference
-          const int r = (lo & 1) * 2 + ((lo >> 1) & 1), col = tid + (lo >> 2);  // the owner's row and column
-          return s_vbase[r][col] + __popc((unsigned)s_mask[r][col] & ((1u << d) - 1u));
-        };
-        const bool flip = (((kFlip >> m) & 1u) != 0u) != (kOdd[t] != 0);
-        int tri[2][3];
-        if (pc == 2) {
-          int in[2], out[2], ni = 0, no = 0;
-          for (int c = 0; c < 4; ++c) {
-            if ((m >> c) & 1u) in[ni++] = c;
-            else out[no++] = c;
-          }
-          const int ac = edge(in[0], out[0]), ad = edge(in[0], out[1]), bd = edge(in[1], out[1]), bc = edge(in[1], out[0]);
-          tri[0][0] = ac, tri[0][1] = ad, tri[0][2] = bd;
-          tri[1][0] = ac, tri[1][1] = bd, tri[1][2] = bc;
-        } else {
-          const unsigned lone = pc == 1 ? m : (~m & 15u);
-          const int c0i = __ffs((int)lone) - 1;
-          int n = 0;
-          for (int c = 0; c < 4; ++c)
-            if (c != c0i) tri[0][n++] = edge(c0i, c);
-        }
-        for (int q = 0; q < (pc == 2 ? 2 : 1); ++q) {
-          if (at >= 0 && at < n_faces) {
-            faces[3 * at] = tri[q][0];
-            faces[3 * at + 1] = tri[q][flip ? 2 : 1];
-            faces[3 * at + 2] = tri[q][flip ? 1 : 2];
-          }
-          ++at;
-        }
-      }
-    }
+    const auto vertex_of = [&](int lo, int d) {
+      const int r = (lo & 1) * 2 + ((lo >> 1) & 1), col = tid + (lo >> 2);  // the owner's row and column
+      return s_vbase[r][col] + __popc((unsigned)s_mask[r][col] & ((1u << d) - 1u));
+    };
+    emit_cell_faces(corners, running_f + (int64_t)((excl >> (4 * kField)) & kFieldMask), 0, n_faces, faces, vertex_of);
 #pragma unroll
     for (int r = 0; r < 4; ++r) running[r] += (int64_t)((total >> (r * kField)) & kFieldMask);
     running_f += (int64_t)((total >> (4 * kField)) & kFieldMask);
     __syncthreads();  // the chunk's LDS has been read
   }
 }
-
-int bad(const char *what) {
-  mf::set_last_error(hipErrorInvalidValue, what);
-  return -(int)hipErrorInvalidValue;
-}
-
-bool bad_dims(int32_t nx, int32_t ny, int32_t nz) {
-  return nx < 2 || ny < 2 || nz < 2 || (int64_t)nx * ny * nz >= ((int64_t)1 << 31);
-}
-
-bool misaligned(const void *p) { return ((uintptr_t)p & 15u) != 0; }
-
-int64_t align16(int64_t n) { return (n + 15) & ~(int64_t)15; }
 
 struct Parts {
   uint8_t *flags, *masks;
@@ -423,13 +328,13 @@ Parts parts_of(const void *workspace, int64_t n) {
 }  // namespace
 
 extern "C" int64_t mf_tsdfmesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
-  if (bad_dims(nx, ny, nz)) return -1;
+  if (bad_volume(nx, ny, nz)) return -1;
   return 2 * align16((int64_t)nx * ny * nz) + ((int64_t)ny * nz + 1) * 16;
 }
 
 extern "C" int mf_tsdfmesh_count(const float *volume, int32_t nx, int32_t ny, int32_t nz, double min_weight,
                                  void *workspace, int64_t *totals, mfStream_t stream) {
-  if (bad_dims(nx, ny, nz) || !(min_weight > 0.0))
+  if (bad_volume(nx, ny, nz) || !(min_weight > 0.0))
     return bad("mf_tsdfmesh_count: nx, ny, nz >= 2 with fewer than 2^31 voxels, min_weight > 0");
   if (!volume || !workspace || !totals) return bad("mf_tsdfmesh_count: null volume, workspace or totals");
   if (misaligned(volume) || misaligned(workspace)) return bad("mf_tsdfmesh_count: volume and workspace 16-byte aligned");
@@ -449,7 +354,7 @@ extern "C" int mf_tsdfmesh_emit(const float *volume, int32_t nx, int32_t ny, int
                                 const void *workspace, int64_t n_vertices, int64_t n_faces, double *vertices,
                                 int32_t *faces, double *normals, mfStream_t stream) {
   const int64_t cap = (int64_t)1 << 31;
-  if (bad_dims(nx, ny, nz) || !(pitch > 0.0) || !(min_weight > 0.0) || n_vertices < 0 || n_vertices >= cap ||
+  if (bad_volume(nx, ny, nz) || !(pitch > 0.0) || !(min_weight > 0.0) || n_vertices < 0 || n_vertices >= cap ||
       n_faces < 0 || n_faces >= cap)
     return bad("mf_tsdfmesh_emit: nx, ny, nz >= 2 with fewer than 2^31 voxels, pitch > 0, min_weight > 0, "
                "0 <= n_vertices, n_faces < 2^31");

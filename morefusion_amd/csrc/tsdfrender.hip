@@ -12,14 +12,18 @@
 //                         "seen").  The last lane of every block also reads the block's halo voxel.  A block is B
 //                         consecutive lanes of one wave: two ballots reduce it, its first lane puts the code into LDS,
 //                         and the workgroup stores its codes as one run of bytes.  OR has no order.
-//   k_tsdf_render         a lane per pixel in 16 x 16 tiles: k_tsdf_raycast's march (the sample body is that kernel's
-//                         text), with one summary byte read per sample in place of the 64 bytes of a FREE or UNKNOWN
-//                         block, and a verified jump to the last sample inside such a block.
+//   k_tsdf_render         a lane per pixel in 16 x 16 tiles: k_tsdf_raycast's march (the ray set-up, the sample and
+//                         the hit rule are tsdf_ray.h's, one text for both kernels), with one summary byte read per
+//                         sample in place of the 64 bytes of a FREE or UNKNOWN block, and a verified jump to the last
+//                         sample inside such a block.  The label tail is tsdf_voxel.h's label_at, which is all of
+//                         k_tsdf_label_image.
 //
 // No atomics.  Nothing is contracted (-ffp-contract=off); only + - * / and floor are used on coordinates.
 #include <math.h>
 
+#include "host_args.h"
 #include "mf_common.h"
+#include "tsdf_ray.h"
 #include "tsdf_voxel.h"
 
 namespace {
@@ -29,11 +33,6 @@ constexpr int kTile = 16;
 
 using mf_tsdf::Pose;
 using mf_tsdf::load_pose;
-
-// two x-neighbours of the volume: (tsdf, weight) of voxel i and of voxel i + 1 -- 16 bytes at an 8-byte aligned address
-struct __attribute__((aligned(8))) VoxelPair {
-  float f0, w0, f1, w1;
-};
 
 // bit 0: the voxel is not free (not (weight > 0 and tsdf == 1)); bit 1: the voxel was seen (weight > 0)
 __device__ __forceinline__ int voxel_bits(const float2 fw) {
@@ -79,18 +78,6 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_block_summary(const float2 *_
   if (tid < per_chunk && I < nbx) summary[((int64_t)K * nby + J) * nbx + I] = s_code[tid];
 }
 
-// floor((m - o) / pitch + 0.5) per axis -> the flat voxel index, or -1 outside the volume (or for a NaN): "TSDF labels"
-__device__ __forceinline__ int64_t voxel_of(const double (&m)[3], double ox, double oy, double oz, double pitch, int nx,
-                                            int ny, int nz) {
-  const double g0 = floor((m[0] - ox) / pitch + 0.5);
-  const double g1 = floor((m[1] - oy) / pitch + 0.5);
-  const double g2 = floor((m[2] - oz) / pitch + 0.5);
-  if (!(g0 >= 0.0 && g0 <= (double)(nx - 1) && g1 >= 0.0 && g1 <= (double)(ny - 1) && g2 >= 0.0 &&
-        g2 <= (double)(nz - 1)))
-    return -1;
-  return ((int64_t)(int)g2 * ny + (int)g1) * nx + (int)g0;
-}
-
 __global__ void __launch_bounds__(kTile *kTile) k_tsdf_render(
     const float *__restrict__ vol, int nx, int ny, int nz, double ox, double oy, double oz, double pitch, double step,
     double min_depth, double max_depth, int max_steps, int H, int W, double fx, double fy, double cx, double cy,
@@ -103,56 +90,35 @@ __global__ void __launch_bounds__(kTile *kTile) k_tsdf_render(
   const double q0 = ((double)col - cx) / fx, q1 = ((double)row - cy) / fy;
   const double org[3] = {ox, oy, oz};
   const int dims[3] = {nx, ny, nz};
-  double d[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) d[a] = (P.R[3 * a] * q0 + P.R[3 * a + 1] * q1) + P.R[3 * a + 2];
-  double enter = min_depth, leave = max_depth;
-  int code = -1;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double lo = org[a], hi = org[a] + pitch * (double)(dims[a] - 1), o = P.t[a];
-    if (d[a] < 0.0 || d[a] > 0.0) {
-      const double t1 = (lo - o) / d[a], t2 = (hi - o) / d[a];
-      const double tn = t1 < t2 ? t1 : t2, tf = t1 < t2 ? t2 : t1;
-      enter = tn <= enter ? enter : tn;
-      leave = tf >= leave ? leave : tf;
-    } else if (!(d[a] == 0.0 && o >= lo && o <= hi)) {
-      code = MF_TSDF_RAY_MISS;
-    }
-  }
-  if (!(enter <= leave)) code = MF_TSDF_RAY_MISS;
+  double d[3], enter, leave;
+  int code = mf_tsdf::ray_setup(P, q0, q1, org, dims, pitch, min_depth, max_depth, d, enter, leave);
   float out = 0.0f;
   int sampled = 0, visited = 0;
   if (code < 0) {
-    const int64_t sy = nx, sz = (int64_t)nx * ny;
-    const double mx = (double)(nx - 2), my = (double)(ny - 2), mz = (double)(nz - 2);
     const int nbx = ((nx - 2) >> shift) + 1, nby = ((ny - 2) >> shift) + 1;
     bool have = false;
     double prev = 0.0;
-    // the jump: `tried` is the block the last attempt started from (a ray meets a block once), (k_pend, p0 .. p2) a
+    // the jump: `tried` is the block the last attempt started from (a ray meets a block once), (k_pend, pend) a
     // position computed for a sample that the march has yet to reach -- it is used there, not computed again
     int tried = -1, k_pend = -1;
-    double p0 = 0.0, p1 = 0.0, p2 = 0.0;
+    double pend[3] = {0.0, 0.0, 0.0};
     for (int k = 0;; ++k) {
       const double s = enter + (double)k * step;
       if (!(s <= leave)) { code = MF_TSDF_RAY_LEFT; break; }
       if (k >= max_steps) { code = MF_TSDF_RAY_CAP; break; }
-      double g0, g1, g2;
+      double g[3], b[3];
       if (k == k_pend) {
-        g0 = p0, g1 = p1, g2 = p2;
+        g[0] = pend[0], g[1] = pend[1], g[2] = pend[2];
       } else {
-        g0 = ((P.t[0] + s * d[0]) - ox) / pitch;
-        g1 = ((P.t[1] + s * d[1]) - oy) / pitch;
-        g2 = ((P.t[2] + s * d[2]) - oz) / pitch;
+        mf_tsdf::grid_pos(P, d, s, org, pitch, g);
         ++visited;
       }
-      const double b0 = floor(g0), b1 = floor(g1), b2 = floor(g2);
-      if (!(b0 >= 0.0 && b0 <= mx && b1 >= 0.0 && b1 <= my && b2 >= 0.0 && b2 <= mz)) {
+      if (!mf_tsdf::cell_of(g, dims, b)) {
         have = false;
         ++sampled;
         continue;
       }
-      const int I0 = (int)b0 >> shift, I1 = (int)b1 >> shift, I2 = (int)b2 >> shift;
+      const int I0 = (int)b[0] >> shift, I1 = (int)b[1] >> shift, I2 = (int)b[2] >> shift;
       const int blk = (I2 * nby + I1) * nbx + I0;
       const int block_code = summary[blk];
       if (block_code != MF_TSDF_BLOCK_MIXED) {
@@ -181,16 +147,14 @@ __global__ void __launch_bounds__(kTile *kTile) k_tsdf_render(
               sj = enter + (double)kj * step;
             }
             if (kj > k + 1 && sj <= leave) {
-              const double h0 = ((P.t[0] + sj * d[0]) - ox) / pitch;
-              const double h1 = ((P.t[1] + sj * d[1]) - oy) / pitch;
-              const double h2 = ((P.t[2] + sj * d[2]) - oz) / pitch;
+              double h[3], c[3];
+              mf_tsdf::grid_pos(P, d, sj, org, pitch, h);
               ++visited;
-              const double c0 = floor(h0), c1 = floor(h1), c2 = floor(h2);
-              if (c0 >= 0.0 && c0 <= mx && c1 >= 0.0 && c1 <= my && c2 >= 0.0 && c2 <= mz &&
-                  ((int)c0 >> shift) == I0 && ((int)c1 >> shift) == I1 && ((int)c2 >> shift) == I2) {
+              if (mf_tsdf::cell_of(h, dims, c) && ((int)c[0] >> shift) == I0 && ((int)c[1] >> shift) == I1 &&
+                  ((int)c[2] >> shift) == I2) {
                 k = kj;  // floor(g_a) is monotone in k: every sample up to kj lies in this block
               } else {
-                k_pend = kj, p0 = h0, p1 = h1, p2 = h2;
+                k_pend = kj, pend[0] = h[0], pend[1] = h[1], pend[2] = h[2];
               }
             }
           }
@@ -198,27 +162,10 @@ __global__ void __launch_bounds__(kTile *kTile) k_tsdf_render(
         continue;
       }
       ++sampled;
-      const float *base = vol + 2 * (((int64_t)(int)b2 * ny + (int)b1) * nx + (int)b0);
-      const VoxelPair v00 = *(const VoxelPair *)base, v10 = *(const VoxelPair *)(base + 2 * sy);
-      const VoxelPair v01 = *(const VoxelPair *)(base + 2 * sz), v11 = *(const VoxelPair *)(base + 2 * (sz + sy));
-      if (!(v00.w0 > 0.0f && v00.w1 > 0.0f && v10.w0 > 0.0f && v10.w1 > 0.0f && v01.w0 > 0.0f && v01.w1 > 0.0f &&
-            v11.w0 > 0.0f && v11.w1 > 0.0f)) { have = false; continue; }
-      const double r0 = g0 - b0, r1 = g1 - b1, r2 = g2 - b2;
-      const double c00 = (double)v00.f0 + r0 * ((double)v00.f1 - (double)v00.f0);
-      const double c10 = (double)v10.f0 + r0 * ((double)v10.f1 - (double)v10.f0);
-      const double c01 = (double)v01.f0 + r0 * ((double)v01.f1 - (double)v01.f0);
-      const double c11 = (double)v11.f0 + r0 * ((double)v11.f1 - (double)v11.f0);
-      const double c0 = c00 + r1 * (c10 - c00), c1 = c01 + r1 * (c11 - c01);
-      const double F = c0 + r2 * (c1 - c0);
-      if (F <= 0.0) {
-        if (have && prev > 0.0) {
-          out = (float)((enter + (double)(k - 1) * step) + step * (prev / (prev - F)));
-          code = MF_TSDF_RAY_HIT;
-        } else {
-          code = MF_TSDF_RAY_BACKFACE;
-        }
-        break;
-      }
+      const mf_tsdf::Cell cell = mf_tsdf::load_cell(vol, nx, ny, b);
+      if (!mf_tsdf::all_seen(cell)) { have = false; continue; }
+      const double F = mf_tsdf::trilinear(cell, g, b);
+      if (F <= 0.0) { code = mf_tsdf::ray_crossing(have, prev, F, enter, step, k, out); break; }
       have = true;
       prev = F;
     }
@@ -231,32 +178,9 @@ __global__ void __launch_bounds__(kTile *kTile) k_tsdf_render(
     // mf_tsdf_label_image on the float32 just stored
     const double dd = (double)out;
     int label = 0;
-    if (dd > 0.0) {
-      const double x = q0 * dd, y = q1 * dd;
-      double m[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) m[a] = ((P.R[3 * a] * x + P.R[3 * a + 1] * y) + P.R[3 * a + 2] * dd) + P.t[a];
-      const int64_t n = voxel_of(m, ox, oy, oz, pitch, nx, ny, nz);
-      if (n >= 0) {
-        const int2 lc = labels[n];
-        if (lc.y >= min_count) label = lc.x;
-      }
-    }
+    if (dd > 0.0) label = mf_tsdf::label_at(labels, nx, ny, nz, ox, oy, oz, pitch, q0, q1, dd, P, min_count);
     label_out[p] = label;
   }
-}
-
-int bad(const char *what) {
-  mf::set_last_error(hipErrorInvalidValue, what);
-  return -(int)hipErrorInvalidValue;
-}
-
-bool bad_volume(int32_t nx, int32_t ny, int32_t nz) {
-  return nx < 2 || ny < 2 || nz < 2 || (int64_t)nx * ny * nz >= ((int64_t)1 << 31);
-}
-
-bool bad_camera(int32_t H, int32_t W, double fx, double fy) {
-  return H < 1 || W < 1 || H > MF_RENDER_MAX_SIDE || W > MF_RENDER_MAX_SIDE || !(fx > 0.0) || !(fy > 0.0);
 }
 
 // log2 of an allowed block edge, -1 for any other
