@@ -71,10 +71,14 @@ namespace {
 // WRONG results; 2048 / 4096: XCD-contiguous workgroup order forced on / off), and MF_ICC_LDS_PAD, bytes of unused
 // dynamic LDS on top of the fused kernel's -- from ~48 KB on only ONE of its workgroups fits a CU (half the resident
 // waves: the experiment of leaving wave slots to a network running beside it).
-struct IccKnobs { int general, bin_cap, dbg, lds_pad; };
+// MF_ICC_FUSED_FORM=auto|generic (default auto): generic = the kernels that carry every case (k_icc_fused /
+// k_icc_fused_big) even where the batch is eligible for a specialised form -- the same bits, for A/B
+// timing and the bitwise tests of the forms.
+struct IccKnobs { int general, bin_cap, dbg, lds_pad, form_generic; };
 IccKnobs read_icc_knobs() {
   auto num = [](const char *name) { const char *e = getenv(name); return e ? atoi(e) : 0; };
-  IccKnobs k = {num("MF_ICC_GENERAL") != 0, num("MF_ICC_BIN_CAP"), 0, 0};
+  const char *form = getenv("MF_ICC_FUSED_FORM");
+  IccKnobs k = {num("MF_ICC_GENERAL") != 0, num("MF_ICC_BIN_CAP"), 0, 0, form && strcmp(form, "generic") == 0};
 #if MF_ICC_DEBUG_BUILD
   k.dbg = num("MF_ICC_DEBUG");
   k.lds_pad = num("MF_ICC_LDS_PAD");
@@ -90,6 +94,19 @@ struct WsLayout {  // byte offsets of the workspace arrays (IccArgs), records of
 };
 struct IccLaunch { int gx, gy, threads, lds; };  // grid (gx, gy), workgroup size, bytes of dynamic LDS
 enum { kTileAccum = 0, kFused = 1, kFusedBig = 2 };  // the kernel(s) behind k_icc_bin
+// The form of the single-pass kernel a batch runs.  kFormGeneric: k_icc_fused / k_icc_fused_big as they always were.
+// The others: k_icc_fused3<MAXNS> (icc_fused.h), which hard-codes kernel size 3 and therefore needs the PROOF that
+// every grid's ksize_of(thr, pitch) is 3, whatever its pitch: the float32 quotient (thr * pitch) / pitch is within 2 ulp
+// of thr, so ceil of it is 2 or 3 for every pitch exactly when both ends of thr * (1 -+ 1e-6) round up to 2 or 3
+// (ksize_lo_host == ksize_host == 3).  thr = 1 and its neighbours (ksize_of = 1 for some or all grids) and thr just
+// above 3 stay on the kernels that read the size per grid.
+//   every ks == 3 proved   largest scene   form
+//   no                     any             kFormGeneric
+//   yes                    <= 16           kForm3Ns16     k_icc_fused3<16>
+//   yes                    17 .. 64        kForm3Ns64     k_icc_fused3<64>
+//   yes                    65 .. 128       kFormGeneric   (k_icc_fused_big)
+// and kFormGeneric for the two-kernel path and under MF_ICC_FUSED_FORM=generic.
+enum { kFormGeneric = 0, kForm3Ns16 = 1, kForm3Ns64 = 2 };
 
 // Everything the host decides about a batch.  Integers only and no padding (asserted below): its bytes are part of
 // mf_icc_refine's graph key, so whatever can change a captured launch is in the key by construction.
@@ -98,6 +115,8 @@ struct IccPlan {
   int single_pass;  // {0,1} no-entry grids on a tile that fits the workgroup, and no MF_ICC_GENERAL
   int variant;      // kTileAccum / kFused / kFusedBig
   int launches;     // per iteration: 2 or 3
+  int fused_form;   // kFormGeneric / kForm3*: which single-pass kernel (table above)
+  int pad_;         // (0: the plan is hashed by its bytes, in 64-bit words)
   IccLaunch bin, tile, accum, fused, step;  // (tile: also what mf_icc_launch_stage(1) times on a single-pass batch;
                                             // fused: zeros on the two-kernel path)
   int hmax, nbins, n_tab, NB, uniform_ns, xcd_order, bin_cap_force, dbg;  // IccArgs; NB = k_icc_accum's blocks per object
@@ -109,6 +128,13 @@ int ksize_host(float thr) {
   // Upper bound of the per-grid kernel size ksize_of(thr, pitch): the float32 quotient
   // (thr * pitch) / pitch is within 2 ulp of thr (exactly thr for thr = 2, the link's default).
   int ks = (int)ceilf(thr * 1.000001f);
+  if (ks % 2 == 0) ks += 1;
+  return ks;
+}
+
+int ksize_lo_host(float thr) {
+  // Lower bound of the same: ceil of the smallest value the float32 quotient can take (thr less 2 ulp), made odd.
+  int ks = (int)ceilf(thr * 0.999999f);
   if (ks % 2 == 0) ks += 1;
   return ks;
 }
@@ -170,6 +196,9 @@ IccPlan icc_plan(const mfIccBatch *b, const IccKnobs &k) {
   p.dbg = k.dbg;
   p.xcd_order = ((O >= 32) || (k.dbg & 2048)) && !(k.dbg & 4096);
   p.bin_cap_force = k.bin_cap;
+  if (p.single_pass && !k.form_generic && p.variant == kFused && ksize_host(b->voxel_threshold) == 3 &&
+      ksize_lo_host(b->voxel_threshold) == 3)
+    p.fused_form = max_ns > 16 ? kForm3Ns64 : kForm3Ns16;
   // the collision rows: 53 KB at 32, 106 KB at 64 objects; beyond that the single-pass kernel re-uses them chunk by chunk
   const int lds_rows2 = std::min(max_ns, kRows2Chunk) * (kAccThreads / 16) * 13 * (int)sizeof(float);
   p.bin = {p.n_tab, 1, kBinThreads, 0};
@@ -249,8 +278,15 @@ void launch_tile(const IccPlan &p, const IccArgs &a, int par, hipStream_t stream
 void launch_accum(const IccPlan &p, const IccArgs &a, int par, hipStream_t stream) {
   ICC_LAUNCH(k_icc_accum, p.accum, stream, a, par);
 }
+void (*fused_kernel(const IccPlan &p))(IccArgs, int) {
+  switch (p.fused_form) {
+    case kForm3Ns16: return k_icc_fused3<16>;
+    case kForm3Ns64: return k_icc_fused3<kRows2Chunk>;
+    default: return p.variant == kFusedBig ? k_icc_fused_big : k_icc_fused;
+  }
+}
 void launch_fused(const IccPlan &p, const IccArgs &a, int par, hipStream_t stream) {
-  auto *kernel = p.variant == kFusedBig ? k_icc_fused_big : k_icc_fused;
+  auto *kernel = fused_kernel(p);
   if (MF_ICC_DEBUG_BUILD && p.fused.lds > kBigLds) mf::allow_big_lds((const void *)kernel, p.fused.lds);  // (MF_ICC_LDS_PAD)
   ICC_LAUNCH(kernel, p.fused, stream, a, par);
 }
@@ -308,6 +344,8 @@ static int icc_enter(const mfIccBatch *b, IccPlan &p) {
   // collision-moment rows: max_scene_objects x 1664 B of dynamic LDS (106 KB at 64 objects)
   if (int e = mf::allow_big_lds((const void *)k_icc_fused, kBigLds)) return e;
   if (int e = mf::allow_big_lds((const void *)k_icc_fused_big, kBigLds)) return e;
+  if (int e = mf::allow_big_lds((const void *)k_icc_fused3<16>, kBigLds)) return e;
+  if (int e = mf::allow_big_lds((const void *)k_icc_fused3<kRows2Chunk>, kBigLds)) return e;
   if (int e = mf::allow_big_lds((const void *)k_icc_accum, kBigLds)) return e;
   p = icc_plan(b, read_icc_knobs());
   if (!p.ok) {
@@ -335,6 +373,13 @@ extern "C" int mf_icc_plan(const mfIccBatch *batch, int64_t *out, int32_t n) {
   const int defined = (int)(sizeof(slots) / sizeof(slots[0]));
   for (int i = 0; i < std::min((int)n, defined); ++i) out[i] = slots[i];
   return defined;
+}
+
+// Tuning aid and test hook, not part of the interface of include/mfhip.h: the form of the single-pass kernel this
+// batch will run (0 generic, 1 k_icc_fused3<16>, 2 k_icc_fused3<64>; negative: invalid descriptor).  Host arithmetic.
+extern "C" int mf_icc_debug_form(const mfIccBatch *batch) {
+  const IccPlan p = icc_plan(batch, read_icc_knobs());
+  return p.ok ? p.fused_form : -1;
 }
 
 extern "C" int mf_pack_points_sdf(const float *points, const float *sdf, int64_t n, void *pts4,

@@ -145,7 +145,9 @@ struct TileGeom {
   float pitch, trunc, ox, oy, oz;
 };
 
-template <bool BIG, class Stamp>
+// NSU > 0 (the specialised forms): the scene holds at most NSU <= 16 objects -- the object of a colliding point is
+// found by NSU - 1 unrolled compares, and the collision moments are reduced in one trip without a loop.
+template <bool BIG, int NSU, class Stamp>
 __device__ __forceinline__ void icc_voxel_phase(const IccArgs &a, const int par, const TileGeom &tg_, const float ne0,
                                                 const float tg0, uint32_t *s_dist, uint32_t *s_id, float *s_rows2,
                                                 VoxLds &Vx, const float (*s_Rt)[12], const int *s_off, Stamp stamp) {
@@ -280,7 +282,12 @@ __device__ __forceinline__ void icc_voxel_phase(const IccArgs &a, const int par,
     if (live && ne == 0.0f && has_o && go * wo > 0.0f && gw != 0.0f) {
       const int pp = (int)(lo_o / (uint32_t)K);
       int e = 0;  // scene object of the point: independent LDS reads, no dependent search loop
-      for (int k = 1; k < Ns; ++k) e += pp >= s_off[k] ? 1 : 0;
+      if constexpr (NSU > 0) {
+#pragma unroll
+        for (int k = 1; k < NSU; ++k) e += (k < Ns && pp >= s_off[k]) ? 1 : 0;
+      } else {
+        for (int k = 1; k < Ns; ++k) e += pp >= s_off[k] ? 1 : 0;
+      }
       float ux, uy, uz;
       bool ok;
       world_frac_r(s_Rt[e], m_oth, ox, oy, oz, inv_pitch, x, iy, iz, ux, uy, uz, ok);
@@ -345,6 +352,17 @@ __device__ __forceinline__ void icc_voxel_phase(const IccArgs &a, const int par,
     } else {
       atomicAdd(reinterpret_cast<unsigned long long *>(own + kNumF), 1ull);  // -> NaN loss
     }
+  } else if constexpr (NSU > 0) {  // (12 NSU <= kTileThreads - kNumF lanes: one trip, no loop)
+    static_assert(12 * NSU <= kTileThreads - kNumF, "one trip of the collision reduction");
+    long long *po = a.acc_oth + ((int64_t)par * a.O + o) * a.max_ns * 12;
+    const int i = tid - kNumF;
+    if (i < 12 * Ns) {
+      const int e = i / 12, cc = i - 12 * e;
+      float sacc = 0.0f;
+      for (int r = 0; r < n_rows; ++r) sacc += s_rows2[(e * kRows + r) * 13 + cc];
+      const long long xq = isfinite(sacc) ? __double2ll_rn((double)sacc * kFixOth) : 0;
+      if (xq != 0) atomicAdd(reinterpret_cast<unsigned long long *>(po + i), (unsigned long long)xq);
+    }
   } else {  // (one trip up to 37 scene objects; a 64-object scene takes two)
     long long *po = a.acc_oth + ((int64_t)par * a.O + o) * a.max_ns * 12;
     for (int i = tid - kNumF; i < 12 * (BIG ? min(Ns, kRows2Chunk) : Ns); i += kTileThreads - kNumF) {
@@ -391,7 +409,12 @@ __device__ __forceinline__ void icc_voxel_phase(const IccArgs &a, const int par,
   }
 }
 
-template <int KS, int MAXNS>
+// SPEC = false: the body of k_icc_fused / k_icc_fused_big as it always was (every kernel size, scenes of any size).
+// SPEC = true (KS = 3 only; k_icc_fused3 below): what the host decided once for the batch is a constant here -- the
+// prefix table of a grid's bins has KS + 1 entries and fetch selects among KS bins, MAXNS <= 16 sizes the scene tables
+// and unrolls the scene loops of the voxel phase, and scenes of one size take Ns from the arguments, so that the loads
+// of the bin counters do not wait for the scene table's.  Same arithmetic in the same order: the same bits.
+template <int KS, int MAXNS, bool SPEC = false>
 __device__ __forceinline__ void icc_fused_body(const IccArgs &a, const int ks_rt, const int par, FusedLds<MAXNS> &L,
                                                const int o, const int tile_) {
   MF_DYN_LDS(uint32_t, s_tile);  // dist[2][nvh] | id[2][nvh] | rows2[max_ns][32][13] floats
@@ -410,9 +433,11 @@ __device__ __forceinline__ void icc_fused_body(const IccArgs &a, const int ks_rt
   uint32_t *s_dist = s_tile, *s_id = s_tile + 2 * nvh;
   float *s_rows2 = reinterpret_cast<float *>(s_tile + 4 * nvh);
   const int4 meta = a.meta[o];
-  const int ja = meta.x, Ns = meta.y - meta.x;
+  static_assert(!SPEC || KS == 3, "the specialised forms are the 3-cell kernel's");
+  constexpr int NBK = SPEC ? KS : 7;  // bins of a grid a tile reads: entries of the prefix table c[kd][]
+  const int ja = meta.x, Ns = (SPEC && a.uniform_ns > 0) ? a.uniform_ns : meta.y - meta.x;
   // independent loads: bin counts of both grids, capacities, offsets, scalars, scene tables
-  int c[2][8];
+  int c[2][NBK + 1];
   int cap[2], nov[2], tot[2];
   int64_t base_g[2];
   const float pitch = a.pitch[o];
@@ -427,13 +452,13 @@ __device__ __forceinline__ void icc_fused_body(const IccArgs &a, const int ks_rt
                   ? min((int)a.bin_cnt[((int64_t)par * 2 * a.O + g) * nb + nbr], 2 * a.bin_pts[g]) : 0;
     c[kd][0] = 0;
 #pragma unroll
-    for (int b = 0; b < 7; ++b) {
+    for (int b = 0; b < NBK; ++b) {
       int n = 0;
       if (b < ks && (kd == 0 || Ns > 1))
         n = min((int)a.bin_cnt[((int64_t)par * 2 * a.O + g) * nb + (bin0 + b) * kHalves + half], cap[kd]);
       c[kd][b + 1] = c[kd][b] + n;
     }
-    tot[kd] = c[kd][7] + nov[kd];  // the tile's bins, then the grid's overflow list (filtered by fetch)
+    tot[kd] = c[kd][NBK] + nov[kd];  // the tile's bins, then the grid's overflow list (filtered by fetch)
   }
   if (tot[0] + tot[1] == 0) return;  // block-uniform: no record of either grid reaches this tile
   const float ox = a.origin[3 * o], oy = a.origin[3 * o + 1], oz = a.origin[3 * o + 2];
@@ -449,7 +474,7 @@ __device__ __forceinline__ void icc_fused_body(const IccArgs &a, const int ks_rt
     if (MF_DBG(a, 32) && threadIdx.x == 0 && wg < 2048) g_dbg_stamps[wg * 8 + i] = wall_clock64();
   };
   stamp(0);
-  if (MF_DBG(a, 32) && threadIdx.x == 0 && wg < 2048) g_dbg_stamps[wg * 8 + 6] = (unsigned long long)(c[0][7] + c[1][7]);
+  if (MF_DBG(a, 32) && threadIdx.x == 0 && wg < 2048) g_dbg_stamps[wg * 8 + 6] = (unsigned long long)(c[0][NBK] + c[1][NBK]);
 #if MF_ICC_DEBUG_BUILD && defined(__HIP_DEVICE_COMPILE__)  // (GCN registers: not in a host build of this source)
   if (MF_DBG(a, 32) && threadIdx.x == 0 && wg < 2048) {  // where did this workgroup run? (HW_ID: CU / SH / SE; XCC_ID)
     unsigned hw, xcc;
@@ -479,8 +504,8 @@ __device__ __forceinline__ void icc_fused_body(const IccArgs &a, const int ks_rt
   auto fetch = [&](const int kd, const int i, float4 &rv, int &rb) {
     rb = -1;
     if (i >= tot[kd]) return;
-    if (i >= c[kd][7]) {  // overflow record: this tile's iff its plane is in x-h..x+h and its rows touch the half
-      rv = a.rec[base_g[kd] + (int64_t)nbr * cap[kd] + (i - c[kd][7])];
+    if (i >= c[kd][NBK]) {  // overflow record: this tile's iff its plane is in x-h..x+h and its rows touch the half
+      rv = a.rec[base_g[kd] + (int64_t)nbr * cap[kd] + (i - c[kd][NBK])];
       const int pl = (int)roundf(rv.x) - (x - h), iry_ = (int)roundf(rv.y);
       const bool in_half = half == 0 ? (iry_ - h < Dh) : (iry_ + h >= Dh);
       rb = (pl >= 0 && pl < ks && in_half) ? pl : -1;
@@ -488,10 +513,10 @@ __device__ __forceinline__ void icc_fused_body(const IccArgs &a, const int ks_rt
     }
     int b = 0;
 #pragma unroll
-    for (int k = 1; k < 7; ++k) b += (k < ks && i >= c[kd][k]) ? 1 : 0;
+    for (int k = 1; k < NBK; ++k) b += (k < ks && i >= c[kd][k]) ? 1 : 0;
     int cb = 0;
 #pragma unroll
-    for (int k = 1; k < 7; ++k) cb = (k == b) ? c[kd][k] : cb;
+    for (int k = 1; k < NBK; ++k) cb = (k == b) ? c[kd][k] : cb;
     rb = b;
     rv = a.rec[base_g[kd] + (int64_t)((bin0 + b) * kHalves + half) * cap[kd] + (i - cb)];
   };
@@ -580,7 +605,7 @@ __device__ __forceinline__ void icc_fused_body(const IccArgs &a, const int ks_rt
   TileGeom tg_;
   tg_.o = o; tg_.ja = ja; tg_.Ns = Ns; tg_.x = x; tg_.y0 = y0; tg_.nvox = nvox; tg_.nvh = nvh; tg_.Wp = Wp; tg_.D = D;
   tg_.K = K; tg_.pitch = pitch; tg_.trunc = trunc; tg_.ox = ox; tg_.oy = oy; tg_.oz = oz;
-  icc_voxel_phase<(MAXNS > kRows2Chunk)>(a, par, tg_, ne0, tg0, s_dist, s_id, s_rows2, L.v, s_Rt, s_off, stamp);
+  icc_voxel_phase<(MAXNS > kRows2Chunk), (SPEC && MAXNS <= 16 ? MAXNS : 0)>(a, par, tg_, ne0, tg0, s_dist, s_id, s_rows2, L.v, s_Rt, s_off, stamp);
   stamp(4);
 }
 
@@ -617,6 +642,21 @@ __global__ __launch_bounds__(kTileThreads, MF_ICC_FUSED_WPE) void k_icc_fused(Ic
 // scenes of 65 .. 128 objects: the scene tables for 128, the collision rows re-used chunk by chunk (round 6)
 __global__ __launch_bounds__(kTileThreads, MF_ICC_FUSED_WPE) void k_icc_fused_big(IccArgs a, int par) {
   MF_ICC_FUSED_KERNEL_BODY(kMaxSceneObjects)
+}
+
+// The specialised forms: every grid of the batch has kernel size 3 (proved on the host, icc_plan: threshold 2, what
+// every caller of the reference passes) and scenes of at most MAXNS objects.  Only icc_fused_body<3> is compiled in;
+// nothing is selected per workgroup.  The two kernels above stay as they were: every other batch, and
+// MF_ICC_FUSED_FORM=generic, run them.
+template <int MAXNS>
+__global__ __launch_bounds__(kTileThreads, MF_ICC_FUSED_WPE) void k_icc_fused3(IccArgs a, int par) {
+  __shared__ FusedLds<MAXNS> L;
+  int lin = blockIdx.y * gridDim.x + blockIdx.x;
+  const int G_ = gridDim.x * gridDim.y;
+  if (a.xcd_order && (G_ & 7) == 0) lin = (lin & 7) * (G_ >> 3) + (lin >> 3);
+  const int o = lin / (int)gridDim.x;
+  const int tile_ = lin - o * (int)gridDim.x;
+  icc_fused_body<3, MAXNS, true>(a, 3, par, L, o, tile_);
 }
 
 }  // namespace
