@@ -4,7 +4,7 @@ integrate_tracked_frame (one occupancy map per stable id) -> target grids -> Mod
 object is spawned once three of its poses agree).  Prints the id table of every frame.
 
     python examples/multiview_mapping.py [--frames 3] [--model <chainer .npz checkpoint>]
-                                       [--track-camera | --track-model [--save-mesh PATH] [--skip-empty]]
+                                       [--track-camera | --track-model [--save-mesh PATH] [--skip-empty] [--color]]
 
 --track-camera: the sensor pose is CameraTracker.track(depth) (dense depth alignment, frame to frame, anchored at frame
 0's pose) instead of the sequence's ground truth; its error against the ground truth is printed per frame.
@@ -14,6 +14,8 @@ frames were fused into (1 cm voxels over the scene), frame to model instead of f
 and unseen space through a block summary of the volume (the same bytes, so the same poses).
 --save-mesh PATH (with --track-model): after the last frame the fused model is written as a Wavefront OBJ
 (TsdfVolume.extract_mesh, geometry.save_obj).
+--color (with --track-model): the volume is built with colors=True and ModelTracker.track(depth, color=rgb) fuses every
+frame's RGB image next to its depth; with --save-mesh the OBJ carries a colour per vertex (``v x y z r g b``).
 """
 import argparse
 import os
@@ -34,9 +36,9 @@ THRESHOLDS = dict(min_mask=20, min_bbox=30, min_side=24)
 MODEL_VOLUME = dict(dims=(161, 93, 121), pitch=0.01, origin=(-0.8, -0.62, 0.3))
 
 
-def track_camera(camera, depth, T_true, k):
+def track_camera(camera, depth, T_true, k, **fused):
     """CameraTracker's (or ModelTracker's) pose of the frame, and its error against the ground truth on stdout."""
-    T = camera.track(depth).cpu().numpy()
+    T = camera.track(depth, **fused).cpu().numpy()
     D = np.linalg.inv(T_true) @ T
     angle = np.degrees(np.arccos(np.clip((np.trace(D[:3, :3]) - 1) / 2, -1, 1)))
     state = "" if k == 0 else (" LOST" if camera.lost else f" ({int(camera.stats[-1, 0])} pairs)")
@@ -55,6 +57,8 @@ def main():
     ap.add_argument("--save-mesh", metavar="PATH", help="with --track-model: write the fused model as an OBJ")
     ap.add_argument("--skip-empty", action="store_true",
                     help="with --track-model: render the model with empty-space skipping (TsdfVolume.render)")
+    ap.add_argument("--color", action="store_true",
+                    help="with --track-model: fuse the frames' RGB into the model; --save-mesh writes vertex colours")
     args = ap.parse_args()
     if args.track_camera and args.track_model:
         ap.error("--track-camera or --track-model, not both")
@@ -62,6 +66,8 @@ def main():
         ap.error("--save-mesh needs --track-model")
     if args.skip_empty and not args.track_model:
         ap.error("--skip-empty needs --track-model")
+    if args.color and not args.track_model:
+        ap.error("--color needs --track-model")
     frames = morefusion.synthetic.make_tracking_sequence(0, args.frames)
     models = PitchTableModels()
     pitch_of = lambda c: models.get_voxel_pitch(32, int(c))  # noqa: E731
@@ -90,12 +96,12 @@ def main():
     if args.track_model:
         height, width = frames[0]["depth"].shape
         camera = morefusion.contrib.ModelTracker(frames[0]["K"], height, width,
-                                                 morefusion.contrib.TsdfVolume(**MODEL_VOLUME),
+                                                 morefusion.contrib.TsdfVolume(colors=args.color, **MODEL_VOLUME),
                                                  T_first=frames[0]["T_sensor_to_map"], skip_empty=args.skip_empty)
     for k, f in enumerate(frames):
         K, T = f["K"], f["T_sensor_to_map"]
         if camera is not None:
-            T = track_camera(camera, to_gpu(f["depth"]), T, k)
+            T = track_camera(camera, to_gpu(f["depth"]), T, k, **(dict(color=to_gpu(f["rgb"])) if args.color else {}))
         pcd = morefusion.geometry.pointcloud_from_depth(f["depth"], K[0, 0], K[1, 1], K[0, 2], K[1, 2])
         tracked, merged, class_of, _ = tracker.track(to_gpu(pcd.astype(np.float32)), to_gpu(f["label_detected"]),
                                                      f["class_ids_by_detection"], K, T)
@@ -130,9 +136,10 @@ def main():
             voter.append_pose(i, c, pose)
         print(f"frame {k}: {len(ids)} poses, spawned objects {voter.validate()}")
     if args.save_mesh:
-        vertices, faces = camera.volume.extract_mesh()
-        morefusion.geometry.save_obj(args.save_mesh, vertices, faces)
-        print(f"fused model: {len(vertices)} vertices, {len(faces)} faces -> {args.save_mesh}")
+        vertices, faces, *colors = camera.volume.extract_mesh(colors=args.color)
+        morefusion.geometry.save_obj(args.save_mesh, vertices, faces, *colors)
+        coloured = f", {int((colors[0][:, 3] == 255).sum())} of them coloured" if args.color else ""
+        print(f"fused model: {len(vertices)} vertices{coloured}, {len(faces)} faces -> {args.save_mesh}")
     stable = sum(len(t) == 1 for t in ids_of_object.values())
     print(f"stable ids: {stable} of {len(ids_of_object)} objects")
 

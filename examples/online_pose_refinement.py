@@ -8,7 +8,7 @@ before and after the refinement.
 
     python examples/online_pose_refinement.py [--frames 3] [--model <chainer .npz checkpoint>] [--render-service]
                                               [--track-camera | --track-model [--save-mesh PATH]
-                                               [--grids-from-model] [--skip-empty]]
+                                               [--grids-from-model] [--skip-empty] [--color]]
 
 --render-service: the tracker matches against the reference's render-service route (use_render_service,
 OctomapServer.cpp:126-135) -- OctomapServer.grids_in_map_frame meshed and rasterised (contrib.render_voxel_grids) --
@@ -27,6 +27,8 @@ and unseen space through a block summary of the volume (the same bytes, so the s
 instance ids the fused model shows from the frame's pose are printed too, depth and labels from that one render launch.
 --save-mesh PATH (with --track-model): after the last frame the fused model is written as a Wavefront OBJ
 (TsdfVolume.extract_mesh, geometry.save_obj).
+--color (with --track-model): the volume is built with colors=True and ModelTracker.track(depth, color=rgb) fuses every
+frame's RGB image next to its depth (and labels); with --save-mesh the OBJ carries a colour per vertex.
 """
 import argparse
 import os
@@ -73,6 +75,8 @@ def main():
                          "grids from it (InstanceTsdfVolume.publish_grids) instead of from the map server")
     ap.add_argument("--skip-empty", action="store_true",
                     help="with --track-model: render the model with empty-space skipping (TsdfVolume.render)")
+    ap.add_argument("--color", action="store_true",
+                    help="with --track-model: fuse the frames' RGB into the model; --save-mesh writes vertex colours")
     args = ap.parse_args()
     if args.track_camera and args.track_model:
         ap.error("--track-camera or --track-model, not both")
@@ -82,6 +86,8 @@ def main():
         ap.error("--grids-from-model needs --track-model")
     if args.skip_empty and not args.track_model:
         ap.error("--skip-empty needs --track-model")
+    if args.color and not args.track_model:
+        ap.error("--color needs --track-model")
     frames = morefusion.synthetic.make_tracking_sequence(0, args.frames)
     models = PitchTableModels()
     pitch_of = lambda c: models.get_voxel_pitch(32, int(c))  # noqa: E731
@@ -113,13 +119,15 @@ def main():
     if args.track_model:
         height, width = frames[0]["depth"].shape
         volume = (morefusion.contrib.InstanceTsdfVolume if args.grids_from_model else morefusion.contrib.TsdfVolume)
-        camera = morefusion.contrib.ModelTracker(frames[0]["K"], height, width, volume(**MODEL_VOLUME),
+        camera = morefusion.contrib.ModelTracker(frames[0]["K"], height, width,
+                                                 volume(colors=args.color, **MODEL_VOLUME),
                                                  T_first=TO_GROUND @ frames[0]["T_sensor_to_map"],
                                                  skip_empty=args.skip_empty)
     classes = {}  # instance id -> class id, over the frames so far
     for k, f in enumerate(frames):
         K, T = f["K"], TO_GROUND @ f["T_sensor_to_map"]
         pcd = morefusion.geometry.pointcloud_from_depth(f["depth"], K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+        fused = dict(color=to_gpu(f["rgb"])) if args.color else {}
 
         def track_instances(T):
             return tracker.track(to_gpu(pcd.astype(np.float32)), to_gpu(f["label_detected"]),
@@ -133,11 +141,11 @@ def main():
                 found.append(track_instances(T_device.cpu().numpy()))
                 return found[0][0]
 
-            T = track_camera(camera, to_gpu(f["depth"]), T, k, label=label_at)
+            T = track_camera(camera, to_gpu(f["depth"]), T, k, label=label_at, **fused)
             tracked, _, class_of, _ = found[0]
         else:
             if camera is not None:
-                T = track_camera(camera, to_gpu(f["depth"]), T, k)
+                T = track_camera(camera, to_gpu(f["depth"]), T, k, **fused)
             tracked, _, class_of, _ = track_instances(T)
         classes.update({int(i): int(c) for i, c in class_of.items()})
         server.insert_scan(tracker.pts_map.reshape(pcd.shape), tracked, class_of, pitch_of, origin=T[:3, 3])
@@ -154,9 +162,10 @@ def main():
         source = "model" if args.grids_from_model else tracker.render
         print(f"frame {k} ({source}): maps {server.mapping.instance_ids}, published {grids['instance_ids']}")
     if args.save_mesh:
-        vertices, faces = camera.volume.extract_mesh()
-        morefusion.geometry.save_obj(args.save_mesh, vertices, faces)
-        print(f"fused model: {len(vertices)} vertices, {len(faces)} faces -> {args.save_mesh}")
+        vertices, faces, *colors = camera.volume.extract_mesh(colors=args.color)
+        morefusion.geometry.save_obj(args.save_mesh, vertices, faces, *colors)
+        coloured = f", {int((colors[0][:, 3] == 255).sum())} of them coloured" if args.color else ""
+        print(f"fused model: {len(vertices)} vertices{coloured}, {len(faces)} faces -> {args.save_mesh}")
     # the pose stage of the last frame, in the sensor frame: crops -> the server's grids -> the network
     published = grids["instance_ids"]
     crops = morefusion.geometry.instance_crops(to_gpu(f["rgb"]), to_gpu(f["depth"]), K, tracked,

@@ -1638,6 +1638,62 @@ int mf_tsdf_render(const float *volume, int32_t nx, int32_t ny, int32_t nz, doub
                    const uint8_t *summary, int32_t B, const int32_t *labels, int32_t min_count, float *depth_out,
                    uint8_t *code_out, int32_t *label_out, int32_t *stats_out, mfStream_t stream);
 
+/* ---- TSDF colour: a colour per voxel, and the colour of renders and of mesh vertices from it (contrib/tsdf_volume.py,
+ * csrc/tsdfcolor.hip) ----
+ * TsdfVolume(colors=True) (DESIGN.md "TSDF colour"; tests/tsdfcolor_ref.py is the NumPy mirror, bit for bit, written
+ * from this text).  All arrays are DEVICE arrays; every call is asynchronous on `stream`, allocates nothing and never
+ * synchronises.  The VOLUME's voxel order, origin, pitch, POSE and ARITHMETIC are those of "TSDF fusion", T p is that of
+ * "TSDF labels"; the (tsdf, weight) volume itself is neither read nor written by any entry point of this section.  A
+ * lane reads and writes only its own output: no atomics, no result depends on an order.
+ *
+ * COLOURS: float32 [nz][ny][nx][4], the quadruple (r, g, b, colour weight) of voxel (i, j, k) at float index
+ * 4 ((k ny + j) nx + i): 16 bytes per voxel, the array 16-byte aligned.  A fresh tensor is all zeros; the caller fills
+ * it.  A voxel is COLOURED iff its colour weight is > 0 (a NaN weight is not coloured).  r, g, b are on the uint8 scale
+ * 0 .. 255.
+ *
+ * SAMPLE, the colour at a MAP-frame point m -> rgba uint8 [4]:
+ *   g_a = (m_a - origin_a) / pitch,  b_a = floor(g_a),  r_a = g_a - b_a                    (a = x, y, z)
+ *   the point is USABLE iff b_a >= 0 and b_a <= n_a - 2 on every axis (compared as float64; a NaN is not usable):
+ *   mf_tsdf_raycast's rule for a sample.  A point on the last lattice plane, g_a == n_a - 1 exactly, has b_a = n_a - 1
+ *   and is NOT usable, like every point beyond it; one on the first plane, g_a == 0, is.
+ *   not usable: rgba = (0, 0, 0, 0).  Otherwise, over the eight corners (b_x + dx, b_y + dy, b_z + dz) in the order of
+ *   their codes dx * 4 + dy * 2 + dz = 0 .. 7 (dz fastest), with wx = 1 - r_x at dx = 0 and r_x at dx = 1, wy and wz alike:
+ *     w = (wx * wy) * wz;  a corner that is COLOURED adds  S = S + w,  A_c = A_c + w * double(C_c)   (c = r, g, b;
+ *     S and A start at 0.0, the corners are added left to right in code order; other corners add nothing)
+ *   S > 0:  rgba = (q(A_r / S), q(A_g / S), q(A_b / S), 255)
+ *           q(x) = floor(x + 0.5); unless q >= 0: 0; if q > 255: 255; stored as uint8
+ *   else:   rgba = (0, 0, 0, 0)       (no coloured corner, or only coloured corners of weight 0)
+ * rgba images and lists are uint8 [..][4], 4-byte aligned, byte order r, g, b, a.
+ * Refused with -hipErrorInvalidValue (the function's name in mf_last_error_string), on the host and before any launch,
+ * unless: nx, ny, nz >= 2 and nx ny nz < 2^31; pitch > 0; truncation > 0; max_weight >= 1; 1 <= H, W <=
+ * MF_RENDER_MAX_SIDE; fx, fy > 0; 1 <= N < 2^31; the arrays non-null (skip_flag may be null); colors 16-byte aligned,
+ * an rgba `out` 4-byte aligned. */
+/* Fuse the colour image of one depth frame into COLOURS.  One lane per voxel (256-lane workgroups over the flat voxel
+ * index); if skip_flag is non-null and *skip_flag != 0 no lane does anything.  rgb is uint8 [H][W][3].  A voxel takes
+ * the colour of its pixel iff it passes every requirement of mf_tsdf_integrate -- z > 0, (row, col) in range, D > 0,
+ * sdf >= -truncation: they depend on the depth, the pose and the geometry alone, so these are the voxels that
+ * mf_tsdf_integrate of the same arguments writes -- and sdf <= truncation (sdf = D - z, before the clamp): the band in
+ * which mf_tsdf_integrate_labels votes.  With (C_r, C_g, C_b, Wc) the voxel's quadruple, widened, and (row, col) its pixel:
+ *   C_c = float32((C_c * Wc + double(rgb[row][col][c])) / (Wc + 1))            (c = r, g, b)
+ *   w = Wc + 1, if w > max_weight then w = max_weight, colour weight = float32(w).
+ * Any other voxel is not written. */
+int mf_tsdf_integrate_colors(float *colors, int32_t nx, int32_t ny, int32_t nz, double origin_x, double origin_y,
+                             double origin_z, double pitch, double truncation, double max_weight, const float *depth,
+                             const uint8_t *rgb, int32_t H, int32_t W, double fx, double fy, double cx, double cy,
+                             const double *T_sensor_to_map, const int32_t *skip_flag, mfStream_t stream);
+/* The colour under every pixel of a depth image (e.g. mf_tsdf_raycast's or mf_tsdf_render's depth_out from the same
+ * pose).  One lane per pixel (16 x 16 pixel workgroups); out uint8 [H][W][4] is written for EVERY pixel.  Pixel
+ * (row, col) with d = double(depth[row][col]):  unless d > 0: (0, 0, 0, 0).  q as in mf_tsdf_raycast, the camera point
+ * p = (q_0 * d, q_1 * d, d), m = T_sensor_to_map p, out = SAMPLE(m). */
+int mf_tsdf_color_image(const float *colors, int32_t nx, int32_t ny, int32_t nz, double origin_x, double origin_y,
+                        double origin_z, double pitch, const float *depth, int32_t H, int32_t W, double fx, double fy,
+                        double cx, double cy, const double *T_sensor_to_map, uint8_t *out, mfStream_t stream);
+/* The colour at N map-frame points (mesh vertices, instance centres, ICP targets): points float64 [N][3],
+ * out uint8 [N][4] := SAMPLE(points[n]).  One lane per point (256-lane workgroups), every row of out is written. */
+int mf_tsdf_sample_colors(const float *colors, int32_t nx, int32_t ny, int32_t nz, double origin_x, double origin_y,
+                          double origin_z, double pitch, const double *points, int64_t N, uint8_t *out,
+                          mfStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -278,6 +278,9 @@ _SIGNATURES = {
     "mf_tsdf_summary_bytes": ([_i] * 4, _i64),
     "mf_tsdf_block_summary": ([_p] + [_i] * 4 + [_p, _p], _i),
     "mf_tsdf_render": ([_p] + [_i] * 3 + [_d] * 7 + [_i] * 3 + [_d] * 4 + [_p, _p, _i, _p, _i] + [_p] * 5, _i),
+    "mf_tsdf_integrate_colors": ([_p] + [_i] * 3 + [_d] * 6 + [_p, _p, _i, _i] + [_d] * 4 + [_p, _p, _p], _i),
+    "mf_tsdf_color_image": ([_p] + [_i] * 3 + [_d] * 4 + [_p, _i, _i] + [_d] * 4 + [_p, _p, _p], _i),
+    "mf_tsdf_sample_colors": ([_p] + [_i] * 3 + [_d] * 4 + [_p, _i64, _p, _p], _i),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

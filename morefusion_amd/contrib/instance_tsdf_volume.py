@@ -53,10 +53,11 @@ class InstanceTsdfVolume(TsdfVolume):
     """``TsdfVolume`` (same arguments) plus ``labels`` int32 ``[nz, ny, nx, 2]`` of (label, count), (0, 0) when fresh;
     ``max_count`` caps the count (how many contradicting frames a settled voxel outlasts)."""
 
-    def __init__(self, dims, pitch, origin, truncation=None, max_weight=64.0, max_count=64, device=None):
+    def __init__(self, dims, pitch, origin, truncation=None, max_weight=64.0, max_count=64, device=None, colors=False):
         self.max_count = _count(max_count, "max_count")
         self.labels = None
-        super().__init__(dims, pitch, origin, truncation=truncation, max_weight=max_weight, device=device)
+        super().__init__(dims, pitch, origin, truncation=truncation, max_weight=max_weight, device=device,
+                         colors=colors)
 
     def reset(self):
         super().reset()
@@ -67,16 +68,18 @@ class InstanceTsdfVolume(TsdfVolume):
             self.labels.zero_()
         return self
 
-    def integrate(self, depth, K, T_sensor_to_map, label=None, skip_if=None):
+    def integrate(self, depth, K, T_sensor_to_map, label=None, skip_if=None, color=None):
         """``TsdfVolume.integrate``; with ``label`` (an integer [H, W] image, NumPy or tensor) every updated voxel
-        within the truncation of the surface also takes the vote of its pixel.  ``skip_if`` covers both tensors."""
+        within the truncation of the surface also takes the vote of its pixel.  ``skip_if`` covers every tensor.
+        ``color``: as ``TsdfVolume.integrate``'s, fused after the depth and the labels."""
         if label is None:
-            return super().integrate(depth, K, T_sensor_to_map, skip_if=skip_if)
+            return super().integrate(depth, K, T_sensor_to_map, skip_if=skip_if, color=color)
         fx, fy, cx, cy = _camera(K)
         d = _depth_tensor(depth, self.device, 3)
         if d.shape[0] != 1:
             raise ValueError(f"depth must be one [H, W] image, got {tuple(d.shape)}")
         lab = _label_tensor(label, self.device, d.shape[1:])
+        rgb = self._color_image_of(color, d.shape[1:])
         if skip_if is not None:
             if not isinstance(skip_if, torch.Tensor) or skip_if.dtype != torch.int32 or skip_if.numel() < 1:
                 raise TypeError("skip_if must be an int32 tensor on the volume's device")
@@ -89,6 +92,8 @@ class InstanceTsdfVolume(TsdfVolume):
             _lib.ptr(self.volume), _lib.ptr(self.labels), *self.dims, *self.origin, self.pitch, self.truncation,
             self.max_weight, _lib.ptr(d), int(d.shape[1]), int(d.shape[2]), fx, fy, cx, cy, _lib.ptr(T), _lib.ptr(lab),
             self.max_count, _lib.ptr(skip_if), _lib.stream_ptr()), "mf_tsdf_integrate_labels")
+        if rgb is not None:
+            self._integrate_colors(d, rgb, (fx, fy, cx, cy), T, skip_if)
         return self
 
     def label_image(self, depth, K, T_sensor_to_map, min_count=1):

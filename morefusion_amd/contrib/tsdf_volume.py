@@ -10,6 +10,9 @@ estimated pose, ``TsdfVolume.raycast`` renders the fused surface from any pose w
 
 * ``TsdfVolume``: the volume and its two kernels; ``extract_mesh`` takes the fused surface out as a triangle mesh
   with normals (csrc/tsdfmesh.hip, ``mf_tsdfmesh_*``, DESIGN.md "TSDF mesh").
+* ``TsdfVolume(colors=True)``: a float32 colour per voxel fused from the frames' RGB images next to the depth;
+  ``color_image`` colours a render, ``sample_colors`` any map-frame points, ``extract_mesh(colors=True)`` the mesh's
+  vertices (csrc/tsdfcolor.hip, ``mf_tsdf_*_colors`` / ``mf_tsdf_color_image``, DESIGN.md "TSDF colour").
 * ``ModelTracker``: ray-cast, align, integrate per frame; no host synchronisation in the loop, and a lost alignment is
   kept out of the model by the device status word, not by reading it back.
 """
@@ -34,14 +37,25 @@ def _camera(K):
     return fx, fy, cx, cy
 
 
+def _color_tensor(color, device, shape):
+    t = color if isinstance(color, torch.Tensor) else torch.as_tensor(np.asarray(color))
+    if t.dtype != torch.uint8:
+        raise TypeError(f"color must be a uint8 [H, W, 3] image, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape) + (3,):
+        raise ValueError(f"color must be {tuple(shape) + (3,)} like the depth, got {tuple(t.shape)}")
+    return t.detach().to(device=device).contiguous()
+
+
 class TsdfVolume:
     """``dims`` = (nx, ny, nz) voxels of ``pitch`` metres; voxel (i, j, k) has its centre at ``origin + pitch *
     (i, j, k)`` in the map frame.  ``truncation`` (default ``4 * pitch``) is the distance at which the signed distance
     saturates, ``max_weight`` the cap of the running average's weight.  The storage is one float32 tensor
     ``[nz, ny, nx, 2]`` of (tsdf, weight) on ``device`` (default "cuda"; there is no CPU fallback), (1, 0) when fresh;
-    ``.tsdf`` and ``.weight`` are views of it."""
+    ``.tsdf`` and ``.weight`` are views of it.  With ``colors=True`` the volume also owns ``.colors``, float32
+    ``[nz, ny, nx, 4]`` of (r, g, b, colour weight) per voxel, zeros when fresh, r, g, b on the 0 .. 255 scale;
+    ``integrate(..., color=)`` fuses into it.  Without it ``.colors`` is None and nothing is allocated."""
 
-    def __init__(self, dims, pitch, origin, truncation=None, max_weight=64.0, device=None):
+    def __init__(self, dims, pitch, origin, truncation=None, max_weight=64.0, device=None, colors=False):
         dims = tuple(int(n) for n in dims)
         if len(dims) != 3 or min(dims) < 2:
             raise ValueError(f"dims = {dims}: three sizes (nx, ny, nz), each >= 2")
@@ -61,11 +75,14 @@ class TsdfVolume:
         nx, ny, nz = dims
         self.volume = torch.empty((nz, ny, nx, 2), dtype=torch.float32, device=self.device)
         _lib.require_gpu(self.volume)
+        self.colors = torch.empty((nz, ny, nx, 4), dtype=torch.float32, device=self.device) if colors else None
         self.reset()
 
     def reset(self):
         self.volume[..., 0] = 1.0
         self.volume[..., 1] = 0.0
+        if self.colors is not None:
+            self.colors.zero_()
         return self
 
     @property
@@ -86,15 +103,35 @@ class TsdfVolume:
         diagonal = self.pitch * math.sqrt(float((nx - 1) ** 2 + (ny - 1) ** 2 + (nz - 1) ** 2))
         return int(math.floor(diagonal / step)) + 2
 
-    def integrate(self, depth, K, T_sensor_to_map, skip_if=None):
+    def _color_image_of(self, color, shape):
+        """The checked uint8 [H, W, 3] device tensor of ``integrate``'s ``color``; None stays None."""
+        if color is None:
+            return None
+        if self.colors is None:
+            raise TypeError("color= needs a volume built with colors=True")
+        return _color_tensor(color, self.device, shape)
+
+    def _integrate_colors(self, d, rgb, camera, T, skip_if):
+        """``mf_tsdf_integrate_colors`` on the depth tensor, pose tensor and skip word of the integrate just issued."""
+        _lib.require_gpu(self.colors, d, rgb, T)
+        _lib.check(_lib.lib().mf_tsdf_integrate_colors(
+            _lib.ptr(self.colors), *self.dims, *self.origin, self.pitch, self.truncation, self.max_weight, _lib.ptr(d),
+            _lib.ptr(rgb), int(d.shape[1]), int(d.shape[2]), *camera, _lib.ptr(T), _lib.ptr(skip_if),
+            _lib.stream_ptr()), "mf_tsdf_integrate_colors")
+
+    def integrate(self, depth, K, T_sensor_to_map, skip_if=None, color=None):
         """Fuse ``depth`` (float [H, W] in metres, NumPy or tensor; NaN or <= 0: a hole) seen through the pinhole ``K``
         from ``T_sensor_to_map`` ([4, 4]; a float64 device tensor is read in place by the kernel, e.g. the pose
         ``CameraTracker.track`` just returned).  ``skip_if``: an int32 device tensor; if its first word is nonzero
-        when the kernel runs, the call changes nothing (the status of an alignment: lost frames stay out)."""
+        when the kernel runs, the call changes nothing (the status of an alignment: lost frames stay out).
+        ``color`` (a volume with ``colors=True``): the frame's uint8 [H, W, 3] image, NumPy or tensor; after the depth
+        every voxel the frame wrote within the truncation of the surface averages its pixel's colour into ``colors``
+        (a second launch on the same stream, pose tensor and skip word; the (tsdf, weight) bytes are the same)."""
         fx, fy, cx, cy = _camera(K)
         d = _depth_tensor(depth, self.device, 3)
         if d.shape[0] != 1:
             raise ValueError(f"depth must be one [H, W] image, got {tuple(d.shape)}")
+        rgb = self._color_image_of(color, d.shape[1:])
         if skip_if is not None:
             if not isinstance(skip_if, torch.Tensor) or skip_if.dtype != torch.int32 or skip_if.numel() < 1:
                 raise TypeError("skip_if must be an int32 tensor on the volume's device")
@@ -107,7 +144,47 @@ class TsdfVolume:
             _lib.ptr(self.volume), *self.dims, *self.origin, self.pitch, self.truncation, self.max_weight, _lib.ptr(d),
             int(d.shape[1]), int(d.shape[2]), fx, fy, cx, cy, _lib.ptr(T), _lib.ptr(skip_if), _lib.stream_ptr()),
             "mf_tsdf_integrate")
+        if rgb is not None:
+            self._integrate_colors(d, rgb, (fx, fy, cx, cy), T, skip_if)
         return self
+
+    def color_image(self, depth, K, T_sensor_to_map):
+        """The fused colour under every pixel of ``depth`` (float [H, W] seen through ``K`` from ``T_sensor_to_map``;
+        meant for ``raycast``'s or ``render``'s depth from the same pose) -> uint8 [H, W, 4] device tensor of
+        (r, g, b, alpha): the colour at the pixel's point, trilinear over the coloured corners of its cell, alpha 255;
+        (0, 0, 0, 0) where there is no depth, outside the volume and where no corner has a colour."""
+        if self.colors is None:
+            raise TypeError("color_image needs a volume built with colors=True")
+        fx, fy, cx, cy = _camera(K)
+        d = _depth_tensor(depth, self.device, 3)
+        if d.shape[0] != 1:
+            raise ValueError(f"depth must be one [H, W] image, got {tuple(d.shape)}")
+        T = self._pose(T_sensor_to_map)
+        out = torch.empty(tuple(d.shape[1:]) + (4,), dtype=torch.uint8, device=self.device)
+        _lib.require_gpu(self.colors, d, T, out)
+        _lib.check(_lib.lib().mf_tsdf_color_image(
+            _lib.ptr(self.colors), *self.dims, *self.origin, self.pitch, _lib.ptr(d), int(d.shape[1]), int(d.shape[2]),
+            fx, fy, cx, cy, _lib.ptr(T), _lib.ptr(out), _lib.stream_ptr()), "mf_tsdf_color_image")
+        return out
+
+    def sample_colors(self, points):
+        """The fused colour at map-frame ``points`` ([N, 3], NumPy or tensor: mesh vertices, instance centres, ICP
+        targets) -> uint8 [N, 4] device tensor of (r, g, b, alpha), ``color_image``'s rule per point.  No points: an
+        empty tensor and no launch."""
+        if self.colors is None:
+            raise TypeError("sample_colors needs a volume built with colors=True")
+        p = points.detach() if isinstance(points, torch.Tensor) else torch.as_tensor(np.asarray(points))
+        if p.dim() != 2 or p.shape[1] != 3:
+            raise ValueError(f"points must be [N, 3], got {tuple(p.shape)}")
+        p = p.to(device=self.device, dtype=torch.float64).contiguous()
+        out = torch.empty((p.shape[0], 4), dtype=torch.uint8, device=self.device)
+        if p.shape[0] == 0:
+            return out
+        _lib.require_gpu(self.colors, p, out)
+        _lib.check(_lib.lib().mf_tsdf_sample_colors(
+            _lib.ptr(self.colors), *self.dims, *self.origin, self.pitch, _lib.ptr(p), int(p.shape[0]), _lib.ptr(out),
+            _lib.stream_ptr()), "mf_tsdf_sample_colors")
+        return out
 
     def raycast(self, K, T_sensor_to_map, height, width, step=None, min_depth=0.0, max_depth=None, return_code=False):
         """The fused surface seen through ``K`` from ``T_sensor_to_map``: a float32 [height, width] device tensor of
@@ -205,17 +282,21 @@ class TsdfVolume:
         out = (depth,) + ((code,) if return_code else ()) + ((stats,) if return_stats else ())
         return out if len(out) > 1 else depth
 
-    def extract_mesh(self, min_weight=1.0, normals=False):
+    def extract_mesh(self, min_weight=1.0, normals=False, colors=False):
         """The fused surface as a welded triangle mesh (csrc/tsdfmesh.hip, include/mfhip.h "TSDF mesh"): ``(vertices
         float64 [V, 3], faces int32 [F, 3])`` on the volume's device, in the map frame, plus ``normals`` float64
         [V, 3] (unit, towards positive tsdf: out of the surface) when asked for.  The surface is the zero level of
         the tsdf (``tsdf <= 0`` is inside) over the six-tetrahedra subdivision of the cells whose eight corners all
         have ``weight >= min_weight``: what the camera never saw is left out, so the mesh is open where the
         observation ends.  Faces are counter-clockwise seen from the outside; vertex and face order are fixed by the
-        volume alone.  One read-back: the two totals, to size the outputs.  An empty surface gives empty tensors."""
+        volume alone.  One read-back: the two totals, to size the outputs.  An empty surface gives empty tensors.
+        ``colors`` (a volume with ``colors=True``): also ``sample_colors(vertices)``, uint8 [V, 4], last in the tuple;
+        no further read-back."""
         min_weight = float(min_weight)
         if not min_weight > 0:
             raise ValueError(f"min_weight = {min_weight}: must be > 0")
+        if colors and self.colors is None:
+            raise TypeError("extract_mesh(colors=True) needs a volume built with colors=True")
         L = _lib.lib()
         nbytes = L.mf_tsdfmesh_workspace_bytes(*self.dims)
         if nbytes < 0:
@@ -236,7 +317,8 @@ class TsdfVolume:
                 _lib.ptr(self.volume), *self.dims, *self.origin, self.pitch, min_weight, _lib.ptr(workspace),
                 n_vertices, n_faces, _lib.ptr(vertices), _lib.ptr(faces), _lib.ptr(normal), _lib.stream_ptr()),
                 "mf_tsdfmesh_emit")
-        return (vertices, faces, normal) if normals else (vertices, faces)
+        out = (vertices, faces, normal) if normals else (vertices, faces)
+        return out + (self.sample_colors(vertices),) if colors else out
 
 
 class ModelTracker:
@@ -270,14 +352,19 @@ class ModelTracker:
         self._T_first = _pose_tensor(np.eye(4) if T_first is None else T_first, 1, volume.device, "T_first")[0].clone()
         self._T_last = None
 
-    def track(self, depth, label=None):
+    def track(self, depth, label=None, color=None):
         """``label``: the frame's instance labels, fused next to its depth by ``InstanceTsdfVolume.integrate`` under
         the same device skip word (the labels do not move the camera) -- an integer [H, W] image, or a callable that
         gets the pose just found (float64 [4, 4] device tensor) and returns one, for labels that are made with the
-        pose.  None: the plain integrate."""
+        pose.  None: the plain integrate.  ``color``: the frame's uint8 [H, W, 3] image, fused into the colours of a
+        volume built with ``colors=True`` under that skip word too (the colour does not move the camera either)."""
         if label is not None and not hasattr(self.volume, "labels"):
             raise TypeError(f"labels need an InstanceTsdfVolume, the volume is a {type(self.volume).__name__}")
-        labelled = lambda T: {} if label is None else dict(label=label(T) if callable(label) else label)  # noqa: E731
+        if color is not None and self.volume.colors is None:
+            raise TypeError("color= needs a volume built with colors=True")
+        fused = {} if color is None else dict(color=color)
+        labelled = lambda T: dict(fused, **({} if label is None else  # noqa: E731
+                                            dict(label=label(T) if callable(label) else label)))
         d = self.tracker._depth(depth)[0]
         if self._T_last is None:
             self.volume.integrate(d, self.K, self._T_first, **labelled(self._T_first))

@@ -34,11 +34,13 @@ class SolidVoxelGrid:
         return f"SolidVoxelGrid(shape={tuple(self.matrix.shape)}, filled={len(self.points)}, pitch={self.pitch:.6g})"
 
 
-def load_obj(path):
+def load_obj(path, return_colors=False):
     """Wavefront OBJ -> (vertices float64 [V, 3], faces int32 [F, 3]).  Reads ``v`` and ``f`` lines only; face
     corners ``a``, ``a/b``, ``a//c``, ``a/b/c``, 1-based or negative (relative to the vertices read so far);
-    polygons are fan-triangulated (a, b, c), (a, c, d), ..."""
-    verts, faces = [], []
+    polygons are fan-triangulated (a, b, c), (a, c, d), ...  ``return_colors``: -> (vertices, faces, colors), the
+    ``r g b`` that ``v x y z r g b`` lines carry (the vertex-colour extension, 0 .. 1) as float64 [V, 3] with 0 0 0 for a
+    vertex without them, or None if no ``v`` line of the file has a colour."""
+    verts, faces, colors, coloured = [], [], [], False
     with open(path, "r") as fh:
         for line in fh:
             parts = line.split()
@@ -46,6 +48,10 @@ def load_obj(path):
                 continue
             if parts[0] == "v":
                 verts.append([float(x) for x in parts[1:4]])
+                if return_colors:
+                    rgb = [float(x) for x in parts[4:7]]
+                    coloured |= len(rgb) == 3
+                    colors.append(rgb if len(rgb) == 3 else [0.0, 0.0, 0.0])
             elif parts[0] == "f":
                 idx = []
                 for c in parts[1:]:
@@ -57,20 +63,35 @@ def load_obj(path):
     f = np.asarray(faces, np.int64).reshape(-1, 3)
     if f.size and (f.min() < 0 or f.max() >= len(v)):
         raise ValueError(f"{path}: face index outside the {len(v)} vertices")
+    if return_colors:
+        return v, f.astype(np.int32), np.asarray(colors, np.float64).reshape(-1, 3) if coloured else None
     return v, f.astype(np.int32)
 
 
-def save_obj(path, vertices, faces):
+def save_obj(path, vertices, faces, colors=None):
     """(vertices [V, 3], faces [F, 3]; NumPy or tensors) -> a Wavefront OBJ of ``v`` and ``f`` lines that ``load_obj``
-    reads back: faces exactly, vertices to the 17 significant digits written (every float64 survives them)."""
+    reads back: faces exactly, vertices to the 17 significant digits written (every float64 survives them).
+    ``colors``: uint8 [V, 4] (r, g, b, alpha: ``TsdfVolume.sample_colors``) or [V, 3]; the lines become ``v x y z r g b``
+    with r, g, b divided by 255 -- the vertex-colour extension that viewers read -- and 0 0 0 where alpha is 0."""
     v = vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else np.asarray(vertices)
     f = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
     v, f = v.astype(np.float64).reshape(-1, 3), f.astype(np.int64).reshape(-1, 3)
     if f.size and (f.min() < 0 or f.max() >= len(v)):
         raise ValueError(f"face index outside the {len(v)} vertices")
+    if colors is not None:
+        c = colors.detach().cpu().numpy() if isinstance(colors, torch.Tensor) else np.asarray(colors)
+        if c.dtype != np.uint8 or c.ndim != 2 or c.shape[0] != len(v) or c.shape[1] not in (3, 4):
+            raise ValueError(f"colors must be uint8 [{len(v)}, 3 or 4], got {c.dtype} {c.shape}")
+        rgb = c[:, :3].astype(np.float64) / 255.0
+        if c.shape[1] == 4:
+            rgb[c[:, 3] == 0] = 0.0
     with open(path, "w") as fh:
-        for x, y, z in v.tolist():
-            fh.write(f"v {x:.17g} {y:.17g} {z:.17g}\n")
+        if colors is not None:
+            for (x, y, z), (r, g, b) in zip(v.tolist(), rgb.tolist()):
+                fh.write(f"v {x:.17g} {y:.17g} {z:.17g} {r:.17g} {g:.17g} {b:.17g}\n")
+        else:
+            for x, y, z in v.tolist():
+                fh.write(f"v {x:.17g} {y:.17g} {z:.17g}\n")
         for a, b, c in f.tolist():
             fh.write(f"f {a + 1} {b + 1} {c + 1}\n")
 
