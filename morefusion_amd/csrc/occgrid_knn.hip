@@ -26,18 +26,23 @@ __global__ __launch_bounds__(256) void k_occgrid_fwd(const float *__restrict__ p
                                                      float *__restrict__ grid,
                                                      float *__restrict__ dmin_out) {
   __shared__ float4 s_p[kTile];
+  __shared__ int s_nan;  // a point with a NaN coordinate: F.min (:82) is an array min, which propagates it
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   const int V = X * Y * Z;
   const float vi = (float)(v / (Y * Z)), vj = (float)((v / Z) % Y), vk = (float)(v % Z);
   float dmin = INFINITY;
+  if (threadIdx.x == 0) s_nan = 0;
+  __syncthreads();
   for (int base = 0; base < P; base += kTile) {
     const int nt = min(kTile, P - base);
     __syncthreads();
     for (int i = threadIdx.x; i < nt; i += blockDim.x) {
       const int p = base + i;
       // points = (points - origin) / pitch   (occupancy_grid_3d.py:43)
-      s_p[i] = make_float4((points[3 * p] - ox) / pitch, (points[3 * p + 1] - oy) / pitch,
-                           (points[3 * p + 2] - oz) / pitch, 0.0f);
+      const float4 q = make_float4((points[3 * p] - ox) / pitch, (points[3 * p + 1] - oy) / pitch,
+                                   (points[3 * p + 2] - oz) / pitch, 0.0f);
+      s_p[i] = q;
+      if (q.x != q.x || q.y != q.y || q.z != q.z) s_nan = 1;  // d is NaN for every voxel: fminf below would drop it
     }
     __syncthreads();
     if (v < V) {
@@ -51,9 +56,10 @@ __global__ __launch_bounds__(256) void k_occgrid_fwd(const float *__restrict__ p
     }
   }
   if (v < V) {
+    if (s_nan) dmin = __uint_as_float(0x7fc00000u);
     float m = threshold - dmin;
-    m = m > 0.0f ? m : 0.0f;          // relu
-    grid[v] = m < 1.0f ? m : 1.0f;    // minimum(., 1)
+    m = (m > 0.0f || m != m) ? m : 0.0f;          // relu = maximum(., 0): a NaN stays
+    grid[v] = (m < 1.0f || m != m) ? m : 1.0f;    // minimum(., 1)
     dmin_out[v] = dmin;
   }
 }
@@ -87,7 +93,9 @@ __global__ __launch_bounds__(256) void k_occgrid_bwd(const float *__restrict__ g
                            (points[3 * p + 2] - oz) / pitch, 0.0f);
     }
     __syncthreads();
-    if (v < V && g_d != 0.0f) {
+    // dmin == 0: a point ON the voxel centre.  Sqrt.backward divides whatever arrives by 2 y = 0 and x**2 multiplies by
+    // 2 x = 0: 0 * inf where the gradient passes, 0 / 0 where it does not -- NaN either way, as in the reference.
+    if (v < V && (g_d != 0.0f || dmin == 0.0f)) {
       for (int i = 0; i < nt; ++i) {
         const float4 q = s_p[i];
         const float a = vi - q.x, b = vj - q.y, c = vk - q.z;
@@ -106,7 +114,8 @@ __global__ __launch_bounds__(256) void k_occgrid_bwd(const float *__restrict__ g
 
 // ---- A11 geometry.nn ----------------------------------------------------------
 // ssd accumulated x,y,z un-fused (cuComputeDistanceGlobal.cu:64-67), strict '<' while
-// scanning refs in increasing index == argmin's first minimum (knn/nn.py:48).
+// scanning refs in increasing index == argmin's first minimum (knn/nn.py:48).  argmin propagates a
+// NaN: the first NaN distance is the minimum and nothing replaces it.
 __global__ __launch_bounds__(256) void k_nn(const float *__restrict__ ref, int R,
                                             const float *__restrict__ query, int64_t Q,
                                             int64_t *__restrict__ out,
@@ -130,7 +139,7 @@ __global__ __launch_bounds__(256) void k_nn(const float *__restrict__ ref, int R
       const float4 r = s_r[i];
       const float dx = r.x - qx, dy = r.y - qy, dz = r.z - qz;
       const float ssd = (dx * dx + dy * dy) + dz * dz;
-      if (ssd < best) { best = ssd; bi = base + i; }
+      if (ssd < best || (ssd != ssd && best == best)) { best = ssd; bi = base + i; }
     }
   }
   if (qi < Q) {
@@ -143,7 +152,8 @@ __global__ __launch_bounds__(256) void k_nn(const float *__restrict__ ref, int R
 // A workgroup = kIcpTargets target points x kIcpSlices lanes each: the transformed source streams
 // through LDS in tiles, lane `sl` of a target scans sources sl, sl + 32, ... (adjacent lanes read
 // adjacent float4: conflict-free), then the 32 partial (min, arg-min) meet in a 5-step butterfly
-// with argmin's rule (lowest index among equal squared distances).  T x S work spread over
+// with argmin's rule (lowest index among equal squared distances; a NaN beats every number, so a NaN source
+// leaves every target unmatched: NaN < thresh is false).  T x S work spread over
 // T / 8 workgroups: one lane per target (round 1) left a 891-point target on 4 workgroups that
 // each walked all 4740 sources serially -- 400 us per call, measured.
 // out[0] += loss, out[1] += matches, out[4..15] += d loss / d [R|t] (row-major 3x4).
@@ -195,7 +205,7 @@ __global__ __launch_bounds__(256) void k_icp(const float *__restrict__ source_al
       const float4 s = s_s[i];
       const float dx = s.x - tx, dy = s.y - ty, dz = s.z - tz;
       const float ssd = (dx * dx + dy * dy) + dz * dz;
-      if (ssd < best) { best = ssd; bi = base + i; bx = dx; by = dy; bz = dz; }
+      if (ssd < best || (ssd != ssd && best == best)) { best = ssd; bi = base + i; bx = dx; by = dy; bz = dz; }
     }
   }
   // (min, lowest index) over the 32 slices of this target; every lane ends with the winner
@@ -204,7 +214,10 @@ __global__ __launch_bounds__(256) void k_icp(const float *__restrict__ source_al
     const float ob = __shfl_xor(best, off);
     const int oi = __shfl_xor(bi, off);
     const float ox = __shfl_xor(bx, off), oy = __shfl_xor(by, off), oz = __shfl_xor(bz, off);
-    if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; bx = ox; by = oy; bz = oz; }
+    const bool on = ob != ob, bn = best != best;  // F.argmin (:35): a NaN is the minimum, the first one wins
+    if (on ? (!bn || oi < bi) : (!bn && (ob < best || (ob == best && oi < bi)))) {
+      best = ob; bi = oi; bx = ox; by = oy; bz = oz;
+    }
   }
   if (sl == 0) {
     float acc[14];

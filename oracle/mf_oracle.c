@@ -122,11 +122,11 @@ void mfo_occupancy_grid_3d(const float *points, int64_t P, float pitch,
           float a = (float)i - pf[3 * p], b = (float)j - pf[3 * p + 1],
                 c = (float)k - pf[3 * p + 2];
           float d = sqrtf((a * a + b * b) + c * c);
-          if (d < dmin) dmin = d;
+          if (d < dmin || (d != d && dmin == dmin)) dmin = d; /* array min: a NaN propagates */
         }
         float m = threshold - dmin;
-        m = m > 0.0f ? m : 0.0f;
-        grid[((int64_t)i * Y + j) * Z + k] = m < 1.0f ? m : 1.0f;
+        m = (m > 0.0f || m != m) ? m : 0.0f;
+        grid[((int64_t)i * Y + j) * Z + k] = (m < 1.0f || m != m) ? m : 1.0f;
       }
   free(pf);
 }
@@ -146,7 +146,7 @@ void mfo_nn(const float *ref, int64_t R, const float *query, int64_t Q, int64_t 
         float tmp = ref[3 * r + d] - query[3 * q + d];
         ssd += tmp * tmp;
       }
-      if (ssd < best) { best = ssd; bi = r; }
+      if (ssd < best || (ssd != ssd && best == best)) { best = ssd; bi = r; } /* argmin: the first NaN wins */
     }
     out[q] = bi;
   }
@@ -519,7 +519,7 @@ float mfo_icp_loss_grad(const float *source, int64_t S, const float *target, int
         float tmp = src[3 * s + d] - target[3 * k + d];
         ssd += tmp * tmp;
       }
-      if (ssd < best) { best = ssd; bi = s; }
+      if (ssd < best || (ssd != ssd && best == best)) { best = ssd; bi = s; } /* argmin: the first NaN wins */
     }
     if (best < 0.02f) {
       float l = 0.0f;
