@@ -18,7 +18,7 @@ import torch
 
 from .. import _lib
 from .camera_tracking import _depth_tensor
-from .tsdf_volume import TsdfVolume, _camera
+from .tsdf_volume import TsdfVolume, _camera, _view
 
 MAX_INSTANCES = 64    # MF_TSDF_MAX_INSTANCES (include/mfhip.h)
 MAX_GRID_DIM = 256    # MF_TSDF_MAX_GRID_DIM
@@ -74,7 +74,7 @@ class InstanceTsdfVolume(TsdfVolume):
         ``color``: as ``TsdfVolume.integrate``'s, fused after the depth and the labels."""
         if label is None:
             return super().integrate(depth, K, T_sensor_to_map, skip_if=skip_if, color=color)
-        fx, fy, cx, cy = _camera(K)
+        camera = _camera(K)
         d = _depth_tensor(depth, self.device, 3)
         if d.shape[0] != 1:
             raise ValueError(f"depth must be one [H, W] image, got {tuple(d.shape)}")
@@ -89,18 +89,18 @@ class InstanceTsdfVolume(TsdfVolume):
         tensors = (self.volume, self.labels, d, lab, T) + (() if skip_if is None else (skip_if,))
         _lib.require_gpu(*tensors)
         _lib.check(_lib.lib().mf_tsdf_integrate_labels(
-            _lib.ptr(self.volume), _lib.ptr(self.labels), *self.dims, *self.origin, self.pitch, self.truncation,
-            self.max_weight, _lib.ptr(d), int(d.shape[1]), int(d.shape[2]), fx, fy, cx, cy, _lib.ptr(T), _lib.ptr(lab),
-            self.max_count, _lib.ptr(skip_if), _lib.stream_ptr()), "mf_tsdf_integrate_labels")
+            _lib.ptr(self.volume), _lib.ptr(self.labels), *self._grid, self.truncation, self.max_weight, _lib.ptr(d),
+            *_view(d, camera), _lib.ptr(T), _lib.ptr(lab), self.max_count, _lib.ptr(skip_if), _lib.stream_ptr()),
+            "mf_tsdf_integrate_labels")
         if rgb is not None:
-            self._integrate_colors(d, rgb, (fx, fy, cx, cy), T, skip_if)
+            self._integrate_colors(d, rgb, camera, T, skip_if)
         return self
 
     def label_image(self, depth, K, T_sensor_to_map, min_count=1):
         """The fused label under every pixel of ``depth`` (float [H, W] seen through ``K`` from ``T_sensor_to_map``;
         meant for ``raycast``'s render from the same pose) -> int32 [H, W] device tensor: the label of the voxel the
         pixel's point falls into if that voxel's count is >= ``min_count``, else 0; 0 where there is no depth."""
-        fx, fy, cx, cy = _camera(K)
+        camera = _camera(K)
         min_count = _count(min_count, "min_count")
         d = _depth_tensor(depth, self.device, 3)
         if d.shape[0] != 1:
@@ -109,8 +109,8 @@ class InstanceTsdfVolume(TsdfVolume):
         out = torch.empty(tuple(d.shape[1:]), dtype=torch.int32, device=self.device)
         _lib.require_gpu(self.labels, d, T, out)
         _lib.check(_lib.lib().mf_tsdf_label_image(
-            _lib.ptr(self.labels), *self.dims, *self.origin, self.pitch, _lib.ptr(d), int(d.shape[1]), int(d.shape[2]),
-            fx, fy, cx, cy, _lib.ptr(T), min_count, _lib.ptr(out), _lib.stream_ptr()), "mf_tsdf_label_image")
+            _lib.ptr(self.labels), *self._grid, _lib.ptr(d), *_view(d, camera), _lib.ptr(T), min_count, _lib.ptr(out),
+            _lib.stream_ptr()), "mf_tsdf_label_image")
         return out
 
     def render(self, K, T_sensor_to_map, height, width, step=None, min_depth=0.0, max_depth=None, block=8,
@@ -223,7 +223,7 @@ class InstanceTsdfVolume(TsdfVolume):
         _lib.require_gpu(self.volume, self.labels, dev_ids, grid_pitch, dev_centers, Ts, out["origin"],
                          out["grid_target"], out["grid_noentry"], out["grid_nontarget_empty"])
         _lib.check(_lib.lib().mf_tsdf_publish_grids(
-            _lib.ptr(self.volume), _lib.ptr(self.labels), *self.dims, *self.origin, self.pitch, _lib.ptr(dev_ids),
+            _lib.ptr(self.volume), _lib.ptr(self.labels), *self._grid, _lib.ptr(dev_ids),
             _lib.ptr(grid_pitch), _lib.ptr(dev_centers), _lib.ptr(Ts[0]), _lib.ptr(Ts[1]), min_weight, min_count,
             float(empty_above), 0.0 if ground_z is None else float(ground_z), flags, B, dim, _lib.ptr(out["origin"]),
             _lib.ptr(out["grid_target"]), _lib.ptr(out["grid_noentry"]), _lib.ptr(out["grid_nontarget_empty"]),

@@ -37,6 +37,11 @@ def _camera(K):
     return fx, fy, cx, cy
 
 
+def _view(d, camera):
+    """The image and camera arguments of a kernel that reads the depth tensor ``d`` [1, H, W]: H, W, fx, fy, cx, cy."""
+    return (int(d.shape[1]), int(d.shape[2]), *camera)
+
+
 def _color_tensor(color, device, shape):
     t = color if isinstance(color, torch.Tensor) else torch.as_tensor(np.asarray(color))
     if t.dtype != torch.uint8:
@@ -86,6 +91,11 @@ class TsdfVolume:
         return self
 
     @property
+    def _grid(self):
+        """The volume's geometry as the C ABI takes it: nx, ny, nz, origin_x, origin_y, origin_z, pitch."""
+        return (*self.dims, *self.origin, self.pitch)
+
+    @property
     def tsdf(self):
         return self.volume[..., 0]
 
@@ -115,9 +125,8 @@ class TsdfVolume:
         """``mf_tsdf_integrate_colors`` on the depth tensor, pose tensor and skip word of the integrate just issued."""
         _lib.require_gpu(self.colors, d, rgb, T)
         _lib.check(_lib.lib().mf_tsdf_integrate_colors(
-            _lib.ptr(self.colors), *self.dims, *self.origin, self.pitch, self.truncation, self.max_weight, _lib.ptr(d),
-            _lib.ptr(rgb), int(d.shape[1]), int(d.shape[2]), *camera, _lib.ptr(T), _lib.ptr(skip_if),
-            _lib.stream_ptr()), "mf_tsdf_integrate_colors")
+            _lib.ptr(self.colors), *self._grid, self.truncation, self.max_weight, _lib.ptr(d), _lib.ptr(rgb),
+            *_view(d, camera), _lib.ptr(T), _lib.ptr(skip_if), _lib.stream_ptr()), "mf_tsdf_integrate_colors")
 
     def integrate(self, depth, K, T_sensor_to_map, skip_if=None, color=None):
         """Fuse ``depth`` (float [H, W] in metres, NumPy or tensor; NaN or <= 0: a hole) seen through the pinhole ``K``
@@ -127,7 +136,7 @@ class TsdfVolume:
         ``color`` (a volume with ``colors=True``): the frame's uint8 [H, W, 3] image, NumPy or tensor; after the depth
         every voxel the frame wrote within the truncation of the surface averages its pixel's colour into ``colors``
         (a second launch on the same stream, pose tensor and skip word; the (tsdf, weight) bytes are the same)."""
-        fx, fy, cx, cy = _camera(K)
+        camera = _camera(K)
         d = _depth_tensor(depth, self.device, 3)
         if d.shape[0] != 1:
             raise ValueError(f"depth must be one [H, W] image, got {tuple(d.shape)}")
@@ -141,11 +150,10 @@ class TsdfVolume:
         tensors = (self.volume, d, T) + (() if skip_if is None else (skip_if,))
         _lib.require_gpu(*tensors)
         _lib.check(_lib.lib().mf_tsdf_integrate(
-            _lib.ptr(self.volume), *self.dims, *self.origin, self.pitch, self.truncation, self.max_weight, _lib.ptr(d),
-            int(d.shape[1]), int(d.shape[2]), fx, fy, cx, cy, _lib.ptr(T), _lib.ptr(skip_if), _lib.stream_ptr()),
-            "mf_tsdf_integrate")
+            _lib.ptr(self.volume), *self._grid, self.truncation, self.max_weight, _lib.ptr(d), *_view(d, camera),
+            _lib.ptr(T), _lib.ptr(skip_if), _lib.stream_ptr()), "mf_tsdf_integrate")
         if rgb is not None:
-            self._integrate_colors(d, rgb, (fx, fy, cx, cy), T, skip_if)
+            self._integrate_colors(d, rgb, camera, T, skip_if)
         return self
 
     def color_image(self, depth, K, T_sensor_to_map):
@@ -155,7 +163,7 @@ class TsdfVolume:
         (0, 0, 0, 0) where there is no depth, outside the volume and where no corner has a colour."""
         if self.colors is None:
             raise TypeError("color_image needs a volume built with colors=True")
-        fx, fy, cx, cy = _camera(K)
+        camera = _camera(K)
         d = _depth_tensor(depth, self.device, 3)
         if d.shape[0] != 1:
             raise ValueError(f"depth must be one [H, W] image, got {tuple(d.shape)}")
@@ -163,8 +171,8 @@ class TsdfVolume:
         out = torch.empty(tuple(d.shape[1:]) + (4,), dtype=torch.uint8, device=self.device)
         _lib.require_gpu(self.colors, d, T, out)
         _lib.check(_lib.lib().mf_tsdf_color_image(
-            _lib.ptr(self.colors), *self.dims, *self.origin, self.pitch, _lib.ptr(d), int(d.shape[1]), int(d.shape[2]),
-            fx, fy, cx, cy, _lib.ptr(T), _lib.ptr(out), _lib.stream_ptr()), "mf_tsdf_color_image")
+            _lib.ptr(self.colors), *self._grid, _lib.ptr(d), *_view(d, camera), _lib.ptr(T), _lib.ptr(out),
+            _lib.stream_ptr()), "mf_tsdf_color_image")
         return out
 
     def sample_colors(self, points):
@@ -182,8 +190,8 @@ class TsdfVolume:
             return out
         _lib.require_gpu(self.colors, p, out)
         _lib.check(_lib.lib().mf_tsdf_sample_colors(
-            _lib.ptr(self.colors), *self.dims, *self.origin, self.pitch, _lib.ptr(p), int(p.shape[0]), _lib.ptr(out),
-            _lib.stream_ptr()), "mf_tsdf_sample_colors")
+            _lib.ptr(self.colors), *self._grid, _lib.ptr(p), int(p.shape[0]), _lib.ptr(out), _lib.stream_ptr()),
+            "mf_tsdf_sample_colors")
         return out
 
     def raycast(self, K, T_sensor_to_map, height, width, step=None, min_depth=0.0, max_depth=None, return_code=False):
@@ -199,9 +207,8 @@ class TsdfVolume:
         code = torch.empty((height, width), dtype=torch.uint8, device=self.device) if return_code else None
         _lib.require_gpu(self.volume, T, depth)
         _lib.check(_lib.lib().mf_tsdf_raycast(
-            _lib.ptr(self.volume), *self.dims, *self.origin, self.pitch, step, min_depth, max_depth, max_steps,
-            height, width, *camera, _lib.ptr(T), _lib.ptr(depth), _lib.ptr(code), _lib.stream_ptr()),
-            "mf_tsdf_raycast")
+            _lib.ptr(self.volume), *self._grid, step, min_depth, max_depth, max_steps, height, width, *camera,
+            _lib.ptr(T), _lib.ptr(depth), _lib.ptr(code), _lib.stream_ptr()), "mf_tsdf_raycast")
         return (depth, code) if return_code else depth
 
     def _ray_arguments(self, K, height, width, step, min_depth, max_depth):
@@ -263,9 +270,9 @@ class TsdfVolume:
         stats = new(torch.int32, 2) if want_stats else None
         _lib.require_gpu(self.volume, summary, T, depth, *(() if labels is None else (labels,)))
         _lib.check(_lib.lib().mf_tsdf_render(
-            _lib.ptr(self.volume), *self.dims, *self.origin, self.pitch, step, min_depth, max_depth, max_steps,
-            height, width, *camera, _lib.ptr(T), _lib.ptr(summary), int(block), _lib.ptr(labels), int(min_count),
-            _lib.ptr(depth), _lib.ptr(code), _lib.ptr(label), _lib.ptr(stats), _lib.stream_ptr()), "mf_tsdf_render")
+            _lib.ptr(self.volume), *self._grid, step, min_depth, max_depth, max_steps, height, width, *camera,
+            _lib.ptr(T), _lib.ptr(summary), int(block), _lib.ptr(labels), int(min_count), _lib.ptr(depth),
+            _lib.ptr(code), _lib.ptr(label), _lib.ptr(stats), _lib.stream_ptr()), "mf_tsdf_render")
         return depth, label, code, stats
 
     def render(self, K, T_sensor_to_map, height, width, step=None, min_depth=0.0, max_depth=None, block=8,
@@ -314,9 +321,8 @@ class TsdfVolume:
         normal = torch.empty((n_vertices, 3), dtype=torch.float64, device=self.device) if normals else None
         if n_vertices > 0:
             _lib.check(L.mf_tsdfmesh_emit(
-                _lib.ptr(self.volume), *self.dims, *self.origin, self.pitch, min_weight, _lib.ptr(workspace),
-                n_vertices, n_faces, _lib.ptr(vertices), _lib.ptr(faces), _lib.ptr(normal), _lib.stream_ptr()),
-                "mf_tsdfmesh_emit")
+                _lib.ptr(self.volume), *self._grid, min_weight, _lib.ptr(workspace), n_vertices, n_faces,
+                _lib.ptr(vertices), _lib.ptr(faces), _lib.ptr(normal), _lib.stream_ptr()), "mf_tsdfmesh_emit")
         out = (vertices, faces, normal) if normals else (vertices, faces)
         return out + (self.sample_colors(vertices),) if colors else out
 

@@ -25,7 +25,6 @@
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kPad = MF_GRIDMESH_MAX_DIM + 2;  // 34 lattice points per axis at most
 constexpr int kLayer = kPad * kPad;            // points of one x-layer

@@ -24,58 +24,51 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTile = 16;
+using namespace mf_tsdf;
 
-using mf_tsdf::Pose;
-using mf_tsdf::load_pose;
-
-__global__ void __launch_bounds__(kThreads) k_tsdf_integrate(
-    float2 *__restrict__ vol, int nx, int ny, int64_t n_voxels, double ox, double oy, double oz, double pitch,
-    double truncation, double max_weight, const float *__restrict__ depth, int H, int W, double fx, double fy,
-    double cx, double cy, const double *__restrict__ T, const int32_t *__restrict__ skip_flag) {
+__global__ void __launch_bounds__(kThreads) k_tsdf_integrate(float2 *__restrict__ vol, Grid G, Fuse fuse,
+                                                             const float *__restrict__ depth, Camera cam,
+                                                             const double *__restrict__ T,
+                                                             const int32_t *__restrict__ skip_flag) {
   if (skip_flag && *skip_flag != 0) return;
   const int64_t n = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (n >= n_voxels) return;
+  if (n >= G.voxels()) return;
   const Pose P = load_pose(T);
   int64_t pixel;
   double sdf;
-  mf_tsdf::integrate_voxel(vol, n, nx, ny, ox, oy, oz, pitch, truncation, max_weight, depth, H, W, fx, fy, cx, cy, P,
-                           pixel, sdf);
+  mf_tsdf::voxel_body<true>(vol, n, G, fuse, depth, cam, P, pixel, sdf);
 }
 
-__global__ void __launch_bounds__(kTile *kTile) k_tsdf_raycast(
-    const float *__restrict__ vol, int nx, int ny, int nz, double ox, double oy, double oz, double pitch, double step,
-    double min_depth, double max_depth, int max_steps, int H, int W, double fx, double fy, double cx, double cy,
-    const double *__restrict__ T, float *__restrict__ depth_out, uint8_t *__restrict__ code_out) {
+__global__ void __launch_bounds__(kTile *kTile) k_tsdf_raycast(const float *__restrict__ vol, Grid G, March march,
+                                                               Camera cam, const double *__restrict__ T,
+                                                               float *__restrict__ depth_out,
+                                                               uint8_t *__restrict__ code_out) {
   const int col = (int)blockIdx.x * kTile + (int)threadIdx.x, row = (int)blockIdx.y * kTile + (int)threadIdx.y;
-  if (col >= W || row >= H) return;
+  if (col >= cam.W || row >= cam.H) return;
   const Pose P = load_pose(T);
-  const double q0 = ((double)col - cx) / fx, q1 = ((double)row - cy) / fy;
-  const double org[3] = {ox, oy, oz};
-  const int dims[3] = {nx, ny, nz};
-  double d[3], enter, leave;
-  int code = mf_tsdf::ray_setup(P, q0, q1, org, dims, pitch, min_depth, max_depth, d, enter, leave);
+  double q0, q1, d[3], enter, leave;
+  cam.ray(col, row, q0, q1);
+  int code = mf_tsdf::ray_setup(P, q0, q1, G, march, d, enter, leave);
   float out = 0.0f;
   if (code < 0) {
     bool have = false;
     double prev = 0.0;
     for (int k = 0;; ++k) {
-      const double s = enter + (double)k * step;
+      const double s = enter + (double)k * march.step;
       if (!(s <= leave)) { code = MF_TSDF_RAY_LEFT; break; }
-      if (k >= max_steps) { code = MF_TSDF_RAY_CAP; break; }
+      if (k >= march.max_steps) { code = MF_TSDF_RAY_CAP; break; }
       double g[3], b[3];
-      mf_tsdf::grid_pos(P, d, s, org, pitch, g);
-      if (!mf_tsdf::cell_of(g, dims, b)) { have = false; continue; }
-      const mf_tsdf::Cell cell = mf_tsdf::load_cell(vol, nx, ny, b);
+      mf_tsdf::grid_pos(P, d, s, G, g);
+      if (!mf_tsdf::cell_of(g, G, b)) { have = false; continue; }
+      const mf_tsdf::Cell cell = mf_tsdf::load_cell(vol, G, b);
       if (!mf_tsdf::all_seen(cell)) { have = false; continue; }
       const double F = mf_tsdf::trilinear(cell, g, b);
-      if (F <= 0.0) { code = mf_tsdf::ray_crossing(have, prev, F, enter, step, k, out); break; }
+      if (F <= 0.0) { code = mf_tsdf::ray_crossing(have, prev, F, enter, march.step, k, out); break; }
       have = true;
       prev = F;
     }
   }
-  const int64_t p = (int64_t)row * W + col;
+  const int64_t p = cam.pixel(col, row);
   depth_out[p] = out;
   if (code_out) code_out[p] = (uint8_t)code;
 }
@@ -91,10 +84,9 @@ extern "C" int mf_tsdf_integrate(float *volume, int32_t nx, int32_t ny, int32_t 
     return bad("mf_tsdf_integrate: nx, ny, nz >= 2 with fewer than 2^31 voxels, pitch > 0, truncation > 0, "
                "max_weight >= 1, 1 <= H, W <= MF_RENDER_MAX_SIDE, fx, fy > 0");
   if (!volume || !depth || !T_sensor_to_map) return bad("mf_tsdf_integrate: null volume, depth or T_sensor_to_map");
-  const int64_t n = (int64_t)nx * ny * nz;
-  hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                     (hipStream_t)stream, (float2 *)volume, (int)nx, (int)ny, n, origin_x, origin_y, origin_z, pitch,
-                     truncation, max_weight, depth, (int)H, (int)W, fx, fy, cx, cy, T_sensor_to_map, skip_flag);
+  const Grid G = grid_of(nx, ny, nz, origin_x, origin_y, origin_z, pitch);
+  hipLaunchKernelGGL(k_tsdf_integrate, lanes(G.voxels()), dim3(kThreads), 0, (hipStream_t)stream, (float2 *)volume, G,
+                     Fuse{truncation, max_weight}, depth, camera_of(H, W, fx, fy, cx, cy), T_sensor_to_map, skip_flag);
   return mf::check_launch("mf_tsdf_integrate");
 }
 
@@ -108,9 +100,9 @@ extern "C" int mf_tsdf_raycast(const float *volume, int32_t nx, int32_t ny, int3
     return bad("mf_tsdf_raycast: nx, ny, nz >= 2 with fewer than 2^31 voxels, pitch > 0, step > 0, 0 <= min_depth < "
                "max_depth, 1 <= max_steps <= MF_TSDF_MAX_STEPS, 1 <= H, W <= MF_RENDER_MAX_SIDE, fx, fy > 0");
   if (!volume || !T_sensor_to_map || !depth_out) return bad("mf_tsdf_raycast: null volume, T_sensor_to_map or depth_out");
-  hipLaunchKernelGGL(k_tsdf_raycast, dim3((unsigned)((W + kTile - 1) / kTile), (unsigned)((H + kTile - 1) / kTile)),
-                     dim3(kTile, kTile), 0, (hipStream_t)stream, volume, (int)nx, (int)ny, (int)nz, origin_x,
-                     origin_y, origin_z, pitch, step, min_depth, max_depth, (int)max_steps, (int)H, (int)W, fx, fy,
-                     cx, cy, T_sensor_to_map, depth_out, code_out);
+  hipLaunchKernelGGL(k_tsdf_raycast, tiles(H, W), dim3(kTile, kTile), 0, (hipStream_t)stream, volume,
+                     grid_of(nx, ny, nz, origin_x, origin_y, origin_z, pitch),
+                     March{step, min_depth, max_depth, max_steps}, camera_of(H, W, fx, fy, cx, cy), T_sensor_to_map,
+                     depth_out, code_out);
   return mf::check_launch("mf_tsdf_raycast");
 }

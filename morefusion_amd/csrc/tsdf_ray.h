@@ -18,16 +18,15 @@ struct __attribute__((aligned(8))) VoxelPair {
 // The ray of camera point (q0, q1, 1): its direction d in the map frame and the depths [enter, leave] at which it is
 // inside both [min_depth, max_depth] and the box of the voxel centres -> MF_TSDF_RAY_MISS for a ray that is never
 // inside, -1 (no code yet) for one to march.
-__device__ __forceinline__ int ray_setup(const Pose &P, double q0, double q1, const double (&org)[3],
-                                         const int (&dims)[3], double pitch, double min_depth, double max_depth,
+__device__ __forceinline__ int ray_setup(const Pose &P, double q0, double q1, const Grid &G, const March &march,
                                          double (&d)[3], double &enter, double &leave) {
 #pragma unroll
   for (int a = 0; a < 3; ++a) d[a] = (P.R[3 * a] * q0 + P.R[3 * a + 1] * q1) + P.R[3 * a + 2];
-  enter = min_depth, leave = max_depth;
+  enter = march.min_depth, leave = march.max_depth;
   int code = -1;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const double lo = org[a], hi = org[a] + pitch * (double)(dims[a] - 1), o = P.t[a];
+    const double lo = G.o[a], hi = G.centre(a, G.n[a] - 1), o = P.t[a];
     if (d[a] < 0.0 || d[a] > 0.0) {
       const double t1 = (lo - o) / d[a], t2 = (hi - o) / d[a];
       const double tn = t1 < t2 ? t1 : t2, tf = t1 < t2 ? t2 : t1;
@@ -42,18 +41,17 @@ __device__ __forceinline__ int ray_setup(const Pose &P, double q0, double q1, co
 }
 
 // the sample at depth s along the ray, in voxel units: g = ((t + s d) - o) / pitch
-__device__ __forceinline__ void grid_pos(const Pose &P, const double (&d)[3], double s, const double (&org)[3],
-                                         double pitch, double (&g)[3]) {
+__device__ __forceinline__ void grid_pos(const Pose &P, const double (&d)[3], double s, const Grid &G, double (&g)[3]) {
 #pragma unroll
-  for (int a = 0; a < 3; ++a) g[a] = ((P.t[a] + s * d[a]) - org[a]) / pitch;
+  for (int a = 0; a < 3; ++a) g[a] = ((P.t[a] + s * d[a]) - G.o[a]) / G.pitch;
 }
 
 // b = floor(g) -> true iff b is a cell of the volume: the eight voxels b .. b + 1 exist
-__device__ __forceinline__ bool cell_of(const double (&g)[3], const int (&dims)[3], double (&b)[3]) {
+__device__ __forceinline__ bool cell_of(const double (&g)[3], const Grid &G, double (&b)[3]) {
 #pragma unroll
   for (int a = 0; a < 3; ++a) b[a] = floor(g[a]);
-  return b[0] >= 0.0 && b[0] <= (double)(dims[0] - 2) && b[1] >= 0.0 && b[1] <= (double)(dims[1] - 2) && b[2] >= 0.0 &&
-         b[2] <= (double)(dims[2] - 2);
+  return b[0] >= 0.0 && b[0] <= (double)(G.n[0] - 2) && b[1] >= 0.0 && b[1] <= (double)(G.n[1] - 2) && b[2] >= 0.0 &&
+         b[2] <= (double)(G.n[2] - 2);
 }
 
 // the eight voxels of cell b: 4 loads of 16 bytes, v[dz][dy] = the x-neighbours (b0, b1 + dy, b2 + dz), (b0 + 1, ..)
@@ -61,9 +59,9 @@ struct Cell {
   VoxelPair v[2][2];
 };
 
-__device__ __forceinline__ Cell load_cell(const float *vol, int nx, int ny, const double (&b)[3]) {
-  const int64_t sy = nx, sz = (int64_t)nx * ny;
-  const float *base = vol + 2 * (((int64_t)(int)b[2] * ny + (int)b[1]) * nx + (int)b[0]);
+__device__ __forceinline__ Cell load_cell(const float *vol, const Grid &G, const double (&b)[3]) {
+  const int64_t sy = G.n[0], sz = (int64_t)G.n[0] * G.n[1];
+  const float *base = vol + 2 * G.flat((int)b[0], (int)b[1], (int)b[2]);
   return {{{*(const VoxelPair *)base, *(const VoxelPair *)(base + 2 * sy)},
            {*(const VoxelPair *)(base + 2 * sz), *(const VoxelPair *)(base + 2 * (sz + sy))}}};
 }

@@ -6,7 +6,7 @@
 // model.
 //
 //   k_tsdf_integrate_colors  a lane per voxel, x fastest: the requirements of k_tsdf_integrate (tsdf_voxel.h's
-//                            project_voxel, the same text: the voxels that take a colour are among those it writes),
+//                            voxel_body<false>, the same text: the voxels that take a colour are among those it writes),
 //                            the band sdf <= truncation of k_tsdf_integrate_labels, then one running average on the
 //                            voxel's own (r, g, b, weight): a 16-byte load and a 16-byte store, contiguous over a wave.
 //                            The (tsdf, weight) volume is not touched.
@@ -25,11 +25,7 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTile = 16;
-
-using mf_tsdf::Pose;
-using mf_tsdf::load_pose;
+using namespace mf_tsdf;
 
 // q of the header: floor(x + 0.5) clamped to 0 .. 255, a NaN gives 0
 __device__ __forceinline__ uint32_t quantise(double x) {
@@ -40,17 +36,15 @@ __device__ __forceinline__ uint32_t quantise(double x) {
 }
 
 // SAMPLE of the header at the map point m -> r | g << 8 | b << 16 | a << 24: the four bytes of an rgba element
-__device__ __forceinline__ uint32_t sample_color(const float4 *__restrict__ colors, int nx, int ny, int nz, double ox,
-                                                 double oy, double oz, double pitch, const double (&m)[3]) {
-  const double org[3] = {ox, oy, oz};
-  const int dims[3] = {nx, ny, nz};
+__device__ __forceinline__ uint32_t sample_color(const float4 *__restrict__ colors, const Grid &G,
+                                                 const double (&m)[3]) {
   double g[3], b[3];
 #pragma unroll
-  for (int a = 0; a < 3; ++a) g[a] = (m[a] - org[a]) / pitch;
-  if (!mf_tsdf::cell_of(g, dims, b)) return 0u;
+  for (int a = 0; a < 3; ++a) g[a] = (m[a] - G.o[a]) / G.pitch;
+  if (!mf_tsdf::cell_of(g, G, b)) return 0u;
   const double r0 = g[0] - b[0], r1 = g[1] - b[1], r2 = g[2] - b[2];
   const double wx[2] = {1.0 - r0, r0}, wy[2] = {1.0 - r1, r1}, wz[2] = {1.0 - r2, r2};
-  const float4 *base = colors + (((int64_t)(int)b[2] * ny + (int)b[1]) * nx + (int)b[0]);
+  const float4 *base = colors + G.flat((int)b[0], (int)b[1], (int)b[2]);
   double S = 0.0, A0 = 0.0, A1 = 0.0, A2 = 0.0;
 #pragma unroll
   for (int dx = 0; dx < 2; ++dx) {
@@ -58,7 +52,7 @@ __device__ __forceinline__ uint32_t sample_color(const float4 *__restrict__ colo
     for (int dy = 0; dy < 2; ++dy) {
 #pragma unroll
       for (int dz = 0; dz < 2; ++dz) {
-        const float4 c = base[((int64_t)dz * ny + dy) * nx + dx];
+        const float4 c = base[G.flat(dx, dy, dz)];
         const double w = (wx[dx] * wy[dy]) * wz[dz];
         if (c.w > 0.0f) {
           S = S + w;
@@ -74,19 +68,16 @@ __device__ __forceinline__ uint32_t sample_color(const float4 *__restrict__ colo
 }
 
 __global__ void __launch_bounds__(kThreads) k_tsdf_integrate_colors(
-    float4 *__restrict__ colors, int nx, int ny, int64_t n_voxels, double ox, double oy, double oz, double pitch,
-    double truncation, double max_weight, const float *__restrict__ depth, const uint8_t *__restrict__ rgb, int H,
-    int W, double fx, double fy, double cx, double cy, const double *__restrict__ T,
-    const int32_t *__restrict__ skip_flag) {
+    float4 *__restrict__ colors, Grid G, Fuse fuse, const float *__restrict__ depth, const uint8_t *__restrict__ rgb,
+    Camera cam, const double *__restrict__ T, const int32_t *__restrict__ skip_flag) {
   if (skip_flag && *skip_flag != 0) return;
   const int64_t n = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (n >= n_voxels) return;
+  if (n >= G.voxels()) return;
   const Pose P = load_pose(T);
   int64_t pixel;
   double sdf;
-  if (!mf_tsdf::project_voxel(n, nx, ny, ox, oy, oz, pitch, truncation, depth, H, W, fx, fy, cx, cy, P, pixel, sdf))
-    return;
-  if (!(sdf <= truncation)) return;  // far in front of the surface: that pixel's colour belongs to what lies behind
+  if (!mf_tsdf::voxel_body<false>(nullptr, n, G, fuse, depth, cam, P, pixel, sdf)) return;
+  if (!(sdf <= fuse.truncation)) return;  // far in front of the surface: that pixel's colour belongs to what lies behind
   const uint8_t *px = rgb + 3 * pixel;
   const double p0 = (double)px[0], p1 = (double)px[1], p2 = (double)px[2];
   const float4 c = colors[n];
@@ -95,36 +86,36 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_integrate_colors(
   const double C0 = ((double)c.x * Wc + p0) / w;
   const double C1 = ((double)c.y * Wc + p1) / w;
   const double C2 = ((double)c.z * Wc + p2) / w;
-  if (w > max_weight) w = max_weight;
+  if (w > fuse.max_weight) w = fuse.max_weight;
   colors[n] = make_float4((float)C0, (float)C1, (float)C2, (float)w);
 }
 
-__global__ void __launch_bounds__(kTile *kTile) k_tsdf_color_image(
-    const float4 *__restrict__ colors, int nx, int ny, int nz, double ox, double oy, double oz, double pitch,
-    const float *__restrict__ depth, int H, int W, double fx, double fy, double cx, double cy,
-    const double *__restrict__ T, uint32_t *__restrict__ out) {
+__global__ void __launch_bounds__(kTile *kTile) k_tsdf_color_image(const float4 *__restrict__ colors, Grid G,
+                                                                   const float *__restrict__ depth, Camera cam,
+                                                                   const double *__restrict__ T,
+                                                                   uint32_t *__restrict__ out) {
   const int col = (int)blockIdx.x * kTile + (int)threadIdx.x, row = (int)blockIdx.y * kTile + (int)threadIdx.y;
-  if (col >= W || row >= H) return;
-  const int64_t p = (int64_t)row * W + col;
+  if (col >= cam.W || row >= cam.H) return;
+  const int64_t p = cam.pixel(col, row);
   const double d = (double)depth[p];
   uint32_t rgba = 0u;
   if (d > 0.0) {
     const Pose P = load_pose(T);
-    const double q0 = ((double)col - cx) / fx, q1 = ((double)row - cy) / fy;
-    double m[3];
+    double q0, q1, m[3];
+    cam.ray(col, row, q0, q1);
     mf_tsdf::pixel_point(P, q0, q1, d, m);
-    rgba = sample_color(colors, nx, ny, nz, ox, oy, oz, pitch, m);
+    rgba = sample_color(colors, G, m);
   }
   out[p] = rgba;
 }
 
-__global__ void __launch_bounds__(kThreads) k_tsdf_sample_colors(
-    const float4 *__restrict__ colors, int nx, int ny, int nz, double ox, double oy, double oz, double pitch,
-    const double *__restrict__ points, int64_t n_points, uint32_t *__restrict__ out) {
+__global__ void __launch_bounds__(kThreads) k_tsdf_sample_colors(const float4 *__restrict__ colors, Grid G,
+                                                                 const double *__restrict__ points, int64_t n_points,
+                                                                 uint32_t *__restrict__ out) {
   const int64_t n = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (n >= n_points) return;
   const double m[3] = {points[3 * n], points[3 * n + 1], points[3 * n + 2]};
-  out[n] = sample_color(colors, nx, ny, nz, ox, oy, oz, pitch, m);
+  out[n] = sample_color(colors, G, m);
 }
 
 }  // namespace
@@ -141,10 +132,10 @@ extern "C" int mf_tsdf_integrate_colors(float *colors, int32_t nx, int32_t ny, i
   if (!colors || !depth || !rgb || !T_sensor_to_map)
     return bad("mf_tsdf_integrate_colors: null colors, depth, rgb or T_sensor_to_map");
   if (misaligned(colors)) return bad("mf_tsdf_integrate_colors: colors must be 16-byte aligned");
-  const int64_t n = (int64_t)nx * ny * nz;
-  hipLaunchKernelGGL(k_tsdf_integrate_colors, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                     (hipStream_t)stream, (float4 *)colors, (int)nx, (int)ny, n, origin_x, origin_y, origin_z, pitch,
-                     truncation, max_weight, depth, rgb, (int)H, (int)W, fx, fy, cx, cy, T_sensor_to_map, skip_flag);
+  const Grid G = grid_of(nx, ny, nz, origin_x, origin_y, origin_z, pitch);
+  hipLaunchKernelGGL(k_tsdf_integrate_colors, lanes(G.voxels()), dim3(kThreads), 0, (hipStream_t)stream,
+                     (float4 *)colors, G, Fuse{truncation, max_weight}, depth, rgb, camera_of(H, W, fx, fy, cx, cy),
+                     T_sensor_to_map, skip_flag);
   return mf::check_launch("mf_tsdf_integrate_colors");
 }
 
@@ -159,10 +150,9 @@ extern "C" int mf_tsdf_color_image(const float *colors, int32_t nx, int32_t ny, 
     return bad("mf_tsdf_color_image: null colors, depth, T_sensor_to_map or out");
   if (misaligned(colors) || ((uintptr_t)out & 3u) != 0)
     return bad("mf_tsdf_color_image: colors must be 16-byte aligned, out 4-byte aligned");
-  hipLaunchKernelGGL(k_tsdf_color_image, dim3((unsigned)((W + kTile - 1) / kTile), (unsigned)((H + kTile - 1) / kTile)),
-                     dim3(kTile, kTile), 0, (hipStream_t)stream, (const float4 *)colors, (int)nx, (int)ny, (int)nz,
-                     origin_x, origin_y, origin_z, pitch, depth, (int)H, (int)W, fx, fy, cx, cy, T_sensor_to_map,
-                     (uint32_t *)out);
+  hipLaunchKernelGGL(k_tsdf_color_image, tiles(H, W), dim3(kTile, kTile), 0, (hipStream_t)stream,
+                     (const float4 *)colors, grid_of(nx, ny, nz, origin_x, origin_y, origin_z, pitch), depth,
+                     camera_of(H, W, fx, fy, cx, cy), T_sensor_to_map, (uint32_t *)out);
   return mf::check_launch("mf_tsdf_color_image");
 }
 
@@ -174,8 +164,7 @@ extern "C" int mf_tsdf_sample_colors(const float *colors, int32_t nx, int32_t ny
   if (!colors || !points || !out) return bad("mf_tsdf_sample_colors: null colors, points or out");
   if (misaligned(colors) || ((uintptr_t)out & 3u) != 0)
     return bad("mf_tsdf_sample_colors: colors must be 16-byte aligned, out 4-byte aligned");
-  hipLaunchKernelGGL(k_tsdf_sample_colors, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                     (hipStream_t)stream, (const float4 *)colors, (int)nx, (int)ny, (int)nz, origin_x, origin_y,
-                     origin_z, pitch, points, N, (uint32_t *)out);
+  hipLaunchKernelGGL(k_tsdf_sample_colors, lanes(N), dim3(kThreads), 0, (hipStream_t)stream, (const float4 *)colors,
+                     grid_of(nx, ny, nz, origin_x, origin_y, origin_z, pitch), points, N, (uint32_t *)out);
   return mf::check_launch("mf_tsdf_sample_colors");
 }

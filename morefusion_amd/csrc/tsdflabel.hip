@@ -26,28 +26,22 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTile = 16;
 constexpr int kCols = 10;  // {count, sum i, j, k, min i, j, k, max i, j, k}
 
-using mf_tsdf::Pose;
-using mf_tsdf::load_pose;
+using namespace mf_tsdf;
 
 __global__ void __launch_bounds__(kThreads) k_tsdf_integrate_labels(
-    float2 *__restrict__ vol, int2 *__restrict__ labels, int nx, int ny, int64_t n_voxels, double ox, double oy,
-    double oz, double pitch, double truncation, double max_weight, const float *__restrict__ depth, int H, int W,
-    double fx, double fy, double cx, double cy, const double *__restrict__ T, const int32_t *__restrict__ label_image,
-    int max_count, const int32_t *__restrict__ skip_flag) {
+    float2 *__restrict__ vol, int2 *__restrict__ labels, Grid G, Fuse fuse, const float *__restrict__ depth, Camera cam,
+    const double *__restrict__ T, const int32_t *__restrict__ label_image, int max_count,
+    const int32_t *__restrict__ skip_flag) {
   if (skip_flag && *skip_flag != 0) return;
   const int64_t n = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (n >= n_voxels) return;
+  if (n >= G.voxels()) return;
   const Pose P = load_pose(T);
   int64_t pixel;
   double sdf;
-  if (!mf_tsdf::integrate_voxel(vol, n, nx, ny, ox, oy, oz, pitch, truncation, max_weight, depth, H, W, fx, fy, cx, cy,
-                                P, pixel, sdf))
-    return;
-  if (!(sdf <= truncation)) return;  // far in front of the surface: the tsdf moves, the label does not
+  if (!mf_tsdf::voxel_body<true>(vol, n, G, fuse, depth, cam, P, pixel, sdf)) return;
+  if (!(sdf <= fuse.truncation)) return;  // far in front of the surface: the tsdf moves, the label does not
   const int v = label_image[pixel];
   if (!(v >= 1 || v == -1)) return;
   int2 lc = labels[n];
@@ -62,35 +56,34 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_integrate_labels(
   labels[n] = lc;
 }
 
-__global__ void __launch_bounds__(kTile *kTile) k_tsdf_label_image(
-    const int2 *__restrict__ labels, int nx, int ny, int nz, double ox, double oy, double oz, double pitch,
-    const float *__restrict__ depth, int H, int W, double fx, double fy, double cx, double cy,
-    const double *__restrict__ T, int min_count, int32_t *__restrict__ out) {
+__global__ void __launch_bounds__(kTile *kTile) k_tsdf_label_image(const int2 *__restrict__ labels, Grid G,
+                                                                   const float *__restrict__ depth, Camera cam,
+                                                                   const double *__restrict__ T, int min_count,
+                                                                   int32_t *__restrict__ out) {
   const int col = (int)blockIdx.x * kTile + (int)threadIdx.x, row = (int)blockIdx.y * kTile + (int)threadIdx.y;
-  if (col >= W || row >= H) return;
-  const int64_t p = (int64_t)row * W + col;
+  if (col >= cam.W || row >= cam.H) return;
+  const int64_t p = cam.pixel(col, row);
   const double d = (double)depth[p];
   int label = 0;
   if (d > 0.0) {
     const Pose P = load_pose(T);
-    const double q0 = ((double)col - cx) / fx, q1 = ((double)row - cy) / fy;
-    label = mf_tsdf::label_at(labels, nx, ny, nz, ox, oy, oz, pitch, q0, q1, d, P, min_count);
+    double q0, q1;
+    cam.ray(col, row, q0, q1);
+    label = mf_tsdf::label_at(labels, G, q0, q1, d, P, min_count);
   }
   out[p] = label;
 }
 
-__global__ void __launch_bounds__(kThreads) k_tsdf_stats_init(long long *__restrict__ table, int B, int nx, int ny,
-                                                              int nz) {
+__global__ void __launch_bounds__(kThreads) k_tsdf_stats_init(long long *__restrict__ table, int B, Grid G) {
   const int t = (int)blockIdx.x * kThreads + (int)threadIdx.x;
   if (t >= B * kCols) return;
   const int c = t % kCols;
-  const int dims[3] = {nx, ny, nz};
-  table[t] = c < 4 ? 0 : (c < 7 ? (long long)dims[c - 4] : -1);
+  table[t] = c < 4 ? 0 : (c < 7 ? (long long)G.n[c - 4] : -1);
 }
 
 __global__ void __launch_bounds__(kThreads) k_tsdf_instance_stats(
-    const float2 *__restrict__ vol, const int2 *__restrict__ labels, int nx, int ny, int64_t n_voxels,
-    double min_weight, int min_count, const int32_t *__restrict__ ids, int B, long long *__restrict__ table) {
+    const float2 *__restrict__ vol, const int2 *__restrict__ labels, Grid G, double min_weight, int min_count,
+    const int32_t *__restrict__ ids, int B, long long *__restrict__ table) {
   __shared__ int s_ids[MF_TSDF_MAX_INSTANCES];
   __shared__ long long s_tab[MF_TSDF_MAX_INSTANCES * kCols];  // 64-bit: 256 indices of up to 2^29 do not fit 32
   const int tid = (int)threadIdx.x;
@@ -101,7 +94,7 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_instance_stats(
   }
   __syncthreads();
   const int64_t n = (int64_t)blockIdx.x * kThreads + tid;
-  if (n < n_voxels) {
+  if (n < G.voxels()) {
     const float2 fw = vol[n];
     const int2 lc = labels[n];
     if ((double)fw.y >= min_weight && fw.x <= 0.0f && lc.y >= min_count) {
@@ -112,9 +105,8 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_instance_stats(
         else hi = mid;
       }
       if (lo < B && s_ids[lo] == lc.x) {
-        const int i = (int)(n % nx);
-        const int64_t rest = n / nx;
-        const int idx[3] = {i, (int)(rest % ny), (int)(rest / ny)};
+        int idx[3];
+        G.unflatten(n, idx);
         long long *row = s_tab + lo * kCols;
         atomicAdd((unsigned long long *)&row[0], 1ull);
 #pragma unroll
@@ -138,12 +130,11 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_instance_stats(
 }
 
 __global__ void __launch_bounds__(kThreads) k_tsdf_publish_grids(
-    const float2 *__restrict__ vol, const int2 *__restrict__ labels, int nx, int ny, int nz, double ox, double oy,
-    double oz, double pitch, const int32_t *__restrict__ ids, const double *__restrict__ grid_pitch,
-    const double *__restrict__ center_map, const double *__restrict__ T_map_to_sensor,
-    const double *__restrict__ T_sensor_to_map, double min_weight, int min_count, double empty_above, double ground_z,
-    int flags, int B, int D, double *__restrict__ origin_out, float *__restrict__ grid_target,
-    float *__restrict__ grid_noentry, uint8_t *__restrict__ grid_nte) {
+    const float2 *__restrict__ vol, const int2 *__restrict__ labels, Grid G, const int32_t *__restrict__ ids,
+    const double *__restrict__ grid_pitch, const double *__restrict__ center_map,
+    const double *__restrict__ T_map_to_sensor, const double *__restrict__ T_sensor_to_map, double min_weight,
+    int min_count, double empty_above, double ground_z, int flags, int B, int D, double *__restrict__ origin_out,
+    float *__restrict__ grid_target, float *__restrict__ grid_noentry, uint8_t *__restrict__ grid_nte) {
   const int64_t nvox = (int64_t)D * D * D;
   const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (g >= nvox * B) return;
@@ -167,7 +158,7 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_publish_grids(
   if ((flags & 1) && m[2] < ground_z) {
     ne = 1.0f;  // below the ground plane
   } else {
-    const int64_t n = mf_tsdf::voxel_of(m, ox, oy, oz, pitch, nx, ny, nz);
+    const int64_t n = mf_tsdf::voxel_of(m, G);
     if (n >= 0) {
       const float2 fw = vol[n];
       if ((double)fw.y >= min_weight) {
@@ -202,11 +193,10 @@ extern "C" int mf_tsdf_integrate_labels(float *volume, int32_t *labels, int32_t 
                "max_weight >= 1, 1 <= H, W <= MF_RENDER_MAX_SIDE, fx, fy > 0, max_count >= 1");
   if (!volume || !labels || !depth || !T_sensor_to_map || !label_image)
     return bad("mf_tsdf_integrate_labels: null volume, labels, depth, T_sensor_to_map or label_image");
-  const int64_t n = (int64_t)nx * ny * nz;
-  hipLaunchKernelGGL(k_tsdf_integrate_labels, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                     (hipStream_t)stream, (float2 *)volume, (int2 *)labels, (int)nx, (int)ny, n, origin_x, origin_y,
-                     origin_z, pitch, truncation, max_weight, depth, (int)H, (int)W, fx, fy, cx, cy, T_sensor_to_map,
-                     label_image, (int)max_count, skip_flag);
+  const Grid G = grid_of(nx, ny, nz, origin_x, origin_y, origin_z, pitch);
+  hipLaunchKernelGGL(k_tsdf_integrate_labels, lanes(G.voxels()), dim3(kThreads), 0, (hipStream_t)stream,
+                     (float2 *)volume, (int2 *)labels, G, Fuse{truncation, max_weight}, depth,
+                     camera_of(H, W, fx, fy, cx, cy), T_sensor_to_map, label_image, (int)max_count, skip_flag);
   return mf::check_launch("mf_tsdf_integrate_labels");
 }
 
@@ -219,10 +209,9 @@ extern "C" int mf_tsdf_label_image(const int32_t *labels, int32_t nx, int32_t ny
                "MF_RENDER_MAX_SIDE, fx, fy > 0, min_count >= 1");
   if (!labels || !depth || !T_sensor_to_map || !out)
     return bad("mf_tsdf_label_image: null labels, depth, T_sensor_to_map or out");
-  hipLaunchKernelGGL(k_tsdf_label_image, dim3((unsigned)((W + kTile - 1) / kTile), (unsigned)((H + kTile - 1) / kTile)),
-                     dim3(kTile, kTile), 0, (hipStream_t)stream, (const int2 *)labels, (int)nx, (int)ny, (int)nz,
-                     origin_x, origin_y, origin_z, pitch, depth, (int)H, (int)W, fx, fy, cx, cy, T_sensor_to_map,
-                     (int)min_count, out);
+  hipLaunchKernelGGL(k_tsdf_label_image, tiles(H, W), dim3(kTile, kTile), 0, (hipStream_t)stream, (const int2 *)labels,
+                     grid_of(nx, ny, nz, origin_x, origin_y, origin_z, pitch), depth, camera_of(H, W, fx, fy, cx, cy),
+                     T_sensor_to_map, (int)min_count, out);
   return mf::check_launch("mf_tsdf_label_image");
 }
 
@@ -233,12 +222,12 @@ extern "C" int mf_tsdf_instance_stats(const float *volume, const int32_t *labels
     return bad("mf_tsdf_instance_stats: nx, ny, nz >= 2 with fewer than 2^31 voxels, min_weight > 0, min_count >= 1, "
                "1 <= B <= MF_TSDF_MAX_INSTANCES");
   if (!volume || !labels || !ids || !table) return bad("mf_tsdf_instance_stats: null volume, labels, ids or table");
-  const int64_t n = (int64_t)nx * ny * nz;
-  hipLaunchKernelGGL(k_tsdf_stats_init, dim3((unsigned)((B * kCols + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                     (hipStream_t)stream, (long long *)table, (int)B, (int)nx, (int)ny, (int)nz);
-  hipLaunchKernelGGL(k_tsdf_instance_stats, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                     (hipStream_t)stream, (const float2 *)volume, (const int2 *)labels, (int)nx, (int)ny, n, min_weight,
-                     (int)min_count, ids, (int)B, (long long *)table);
+  const Grid G = grid_of(nx, ny, nz);
+  hipLaunchKernelGGL(k_tsdf_stats_init, lanes(B * kCols), dim3(kThreads), 0, (hipStream_t)stream, (long long *)table,
+                     (int)B, G);
+  hipLaunchKernelGGL(k_tsdf_instance_stats, lanes(G.voxels()), dim3(kThreads), 0, (hipStream_t)stream,
+                     (const float2 *)volume, (const int2 *)labels, G, min_weight, (int)min_count, ids, (int)B,
+                     (long long *)table);
   return mf::check_launch("mf_tsdf_instance_stats");
 }
 
@@ -257,10 +246,9 @@ extern "C" int mf_tsdf_publish_grids(const float *volume, const int32_t *labels,
       !grid_target || !grid_noentry || !grid_nontarget_empty)
     return bad("mf_tsdf_publish_grids: null array");
   const int64_t n = (int64_t)B * D * D * D;  // <= 64 * 256^3 = 2^30
-  hipLaunchKernelGGL(k_tsdf_publish_grids, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                     (hipStream_t)stream, (const float2 *)volume, (const int2 *)labels, (int)nx, (int)ny, (int)nz,
-                     origin_x, origin_y, origin_z, pitch, ids, grid_pitch, center_map, T_map_to_sensor,
-                     T_sensor_to_map, min_weight, (int)min_count, empty_above, ground_z, (int)flags, (int)B, (int)D,
-                     origin, grid_target, grid_noentry, grid_nontarget_empty);
+  hipLaunchKernelGGL(k_tsdf_publish_grids, lanes(n), dim3(kThreads), 0, (hipStream_t)stream, (const float2 *)volume,
+                     (const int2 *)labels, grid_of(nx, ny, nz, origin_x, origin_y, origin_z, pitch), ids, grid_pitch,
+                     center_map, T_map_to_sensor, T_sensor_to_map, min_weight, (int)min_count, empty_above, ground_z,
+                     (int)flags, (int)B, (int)D, origin, grid_target, grid_noentry, grid_nontarget_empty);
   return mf::check_launch("mf_tsdf_publish_grids");
 }

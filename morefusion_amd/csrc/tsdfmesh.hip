@@ -27,10 +27,12 @@
 #include "host_args.h"
 #include "kuhn_mesh.h"
 #include "mf_common.h"
+#include "tsdf_voxel.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+using mf_tsdf::Grid;
+
 constexpr int kWaves = kThreads / 64;
 constexpr int kScanThreads = 1024;
 
@@ -169,19 +171,19 @@ __global__ __launch_bounds__(kScanThreads) void k_tm_scan(int64_t *__restrict__ 
 
 struct Lattice {
   const float2 *vol;
-  int nx, ny, nz;
+  Grid g;
   double min_weight;
 };
 
 // the tsdf gradient at lattice point (i, j, k): central, one-sided or 0 per axis, by what the neighbours allow
 __device__ __forceinline__ void gradient(const Lattice &L, int i, int j, int k, double (&G)[3]) {
-  const int64_t at = ((int64_t)k * L.ny + j) * L.nx + i;
+  const int64_t at = L.g.flat(i, j, k);
   const double F = (double)L.vol[at].x;
-  const int pos[3] = {i, j, k}, dim[3] = {L.nx, L.ny, L.nz};
-  const int64_t stride[3] = {1, L.nx, (int64_t)L.nx * L.ny};
+  const int pos[3] = {i, j, k};
+  const int64_t stride[3] = {1, L.g.n[0], (int64_t)L.g.n[0] * L.g.n[1]};
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    bool hp = pos[c] + 1 < dim[c], hm = pos[c] >= 1;
+    bool hp = pos[c] + 1 < L.g.n[c], hm = pos[c] >= 1;
     double Fp = 0.0, Fm = 0.0;
     if (hp) {
       const float2 v = L.vol[at + stride[c]];
@@ -202,14 +204,14 @@ constexpr unsigned long long kFieldMask = (1ull << kField) - 1ull;
 
 __global__ __launch_bounds__(kThreads) void k_tm_emit(
     const float2 *__restrict__ vol, const uint8_t *__restrict__ flags, const uint8_t *__restrict__ masks,
-    const int64_t *__restrict__ rows, int nx, int ny, int nz, double ox, double oy, double oz, double pitch,
-    double min_weight, int64_t n_vertices, int64_t n_faces, double *__restrict__ vertices, int32_t *__restrict__ faces,
-    double *__restrict__ normals) {
+    const int64_t *__restrict__ rows, Grid G, double min_weight, int64_t n_vertices, int64_t n_faces,
+    double *__restrict__ vertices, int32_t *__restrict__ faces, double *__restrict__ normals) {
   // column kThreads is the first column of the next chunk: the + x corners of the chunk's last cell
   __shared__ unsigned char s_mask[4][kThreads + 1];
   __shared__ int s_vbase[4][kThreads + 1];
   __shared__ unsigned char s_col[kThreads + 1];  // bit 0: the four rows observed at this column; bit 4 + r: inside
   __shared__ unsigned long long s_w[kWaves];
+  const int nx = G.n[0], ny = G.n[1], nz = G.n[2];
   const int64_t row = blockIdx.x;
   const int j = (int)(row % ny), k = (int)(row / ny);
   const int64_t v_row = rows[2 * row], f_row = rows[2 * row + 1];
@@ -225,7 +227,7 @@ __global__ __launch_bounds__(kThreads) void k_tm_emit(
     running[r] = r_ok[r] ? rows[2 * r_row[r]] : 0;
   }
   int64_t running_f = f_row;
-  const Lattice L = {vol, nx, ny, nz, min_weight};
+  const Lattice L = {vol, G, min_weight};
   const int tid = (int)threadIdx.x;
   for (int x0 = 0; x0 < nx; x0 += kThreads) {
     // masks and flags of the chunk's columns, and of the column behind it (lane 0)
@@ -273,7 +275,6 @@ __global__ __launch_bounds__(kThreads) void k_tm_emit(
     if (own[0] != 0u) {
       const int64_t at_a = row * nx + i;
       const double Fa = (double)vol[at_a].x;
-      const double o[3] = {ox, oy, oz};
       const int pa[3] = {i, j, k};
       double Ga[3] = {0.0, 0.0, 0.0};
       if (normals) gradient(L, i, j, k, Ga);
@@ -283,10 +284,10 @@ __global__ __launch_bounds__(kThreads) void k_tm_emit(
         const int code = code_of_dir(d);
         const int e[3] = {(code >> 2) & 1, (code >> 1) & 1, code & 1};
         if (at >= 0 && at < n_vertices) {
-          const double Fb = (double)vol[at_a + ((int64_t)e[2] * ny + e[1]) * nx + e[0]].x;
+          const double Fb = (double)vol[at_a + G.flat(e[0], e[1], e[2])].x;
           const double r = Fa / (Fa - Fb);
           for (int c = 0; c < 3; ++c) {
-            const double p_a = o[c] + pitch * (double)pa[c], p_b = o[c] + pitch * (double)(pa[c] + e[c]);
+            const double p_a = G.centre(c, pa[c]), p_b = G.centre(c, pa[c] + e[c]);
             vertices[3 * at + c] = p_a + r * (p_b - p_a);
           }
           if (normals) {
@@ -341,8 +342,7 @@ extern "C" int mf_tsdfmesh_count(const float *volume, int32_t nx, int32_t ny, in
   const int64_t n = (int64_t)nx * ny * nz, R = (int64_t)ny * nz;
   const Parts p = parts_of(workspace, n);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_tm_flags, dim3((unsigned)(((n + 3) / 4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, volume,
-                     n, min_weight, p.flags);
+  hipLaunchKernelGGL(k_tm_flags, lanes((n + 3) / 4), dim3(kThreads), 0, s, volume, n, min_weight, p.flags);
   hipLaunchKernelGGL(k_tm_count, dim3((unsigned)R), dim3(kThreads), 0, s, (const uint8_t *)p.flags, (int)nx, (int)ny,
                      (int)nz, p.masks, p.rows);
   hipLaunchKernelGGL(k_tm_scan, dim3(1), dim3(kScanThreads), 0, s, p.rows, R, totals);
@@ -360,11 +360,10 @@ extern "C" int mf_tsdfmesh_emit(const float *volume, int32_t nx, int32_t ny, int
                "0 <= n_vertices, n_faces < 2^31");
   if (!volume || !workspace || !vertices || !faces) return bad("mf_tsdfmesh_emit: null volume, workspace, vertices or faces");
   if (misaligned(volume) || misaligned(workspace)) return bad("mf_tsdfmesh_emit: volume and workspace 16-byte aligned");
-  const int64_t n = (int64_t)nx * ny * nz, R = (int64_t)ny * nz;
-  const Parts p = parts_of(workspace, n);
-  hipLaunchKernelGGL(k_tm_emit, dim3((unsigned)R), dim3(kThreads), 0, (hipStream_t)stream, (const float2 *)volume,
-                     (const uint8_t *)p.flags, (const uint8_t *)p.masks, (const int64_t *)p.rows, (int)nx, (int)ny,
-                     (int)nz, origin_x, origin_y, origin_z, pitch, min_weight, n_vertices, n_faces, vertices, faces,
-                     normals);
+  const Grid G = grid_of(nx, ny, nz, origin_x, origin_y, origin_z, pitch);
+  const Parts p = parts_of(workspace, G.voxels());
+  hipLaunchKernelGGL(k_tm_emit, dim3((unsigned)((int64_t)ny * nz)), dim3(kThreads), 0, (hipStream_t)stream,
+                     (const float2 *)volume, (const uint8_t *)p.flags, (const uint8_t *)p.masks,
+                     (const int64_t *)p.rows, G, min_weight, n_vertices, n_faces, vertices, faces, normals);
   return mf::check_launch("mf_tsdfmesh_emit");
 }

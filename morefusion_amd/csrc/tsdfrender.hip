@@ -28,11 +28,7 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTile = 16;
-
-using mf_tsdf::Pose;
-using mf_tsdf::load_pose;
+using namespace mf_tsdf;
 
 // bit 0: the voxel is not free (not (weight > 0 and tsdf == 1)); bit 1: the voxel was seen (weight > 0)
 __device__ __forceinline__ int voxel_bits(const float2 fw) {
@@ -79,23 +75,22 @@ __global__ void __launch_bounds__(kThreads) k_tsdf_block_summary(const float2 *_
 }
 
 __global__ void __launch_bounds__(kTile *kTile) k_tsdf_render(
-    const float *__restrict__ vol, int nx, int ny, int nz, double ox, double oy, double oz, double pitch, double step,
-    double min_depth, double max_depth, int max_steps, int H, int W, double fx, double fy, double cx, double cy,
-    const double *__restrict__ T, const uint8_t *__restrict__ summary, int shift, const int2 *__restrict__ labels,
-    int min_count, float *__restrict__ depth_out, uint8_t *__restrict__ code_out, int32_t *__restrict__ label_out,
+    const float *__restrict__ vol, Grid G, March march, Camera cam, const double *__restrict__ T,
+    const uint8_t *__restrict__ summary, int shift, const int2 *__restrict__ labels, int min_count,
+    float *__restrict__ depth_out, uint8_t *__restrict__ code_out, int32_t *__restrict__ label_out,
     int2 *__restrict__ stats_out) {
   const int col = (int)blockIdx.x * kTile + (int)threadIdx.x, row = (int)blockIdx.y * kTile + (int)threadIdx.y;
-  if (col >= W || row >= H) return;
+  if (col >= cam.W || row >= cam.H) return;
   const Pose P = load_pose(T);
-  const double q0 = ((double)col - cx) / fx, q1 = ((double)row - cy) / fy;
-  const double org[3] = {ox, oy, oz};
-  const int dims[3] = {nx, ny, nz};
-  double d[3], enter, leave;
-  int code = mf_tsdf::ray_setup(P, q0, q1, org, dims, pitch, min_depth, max_depth, d, enter, leave);
+  const double step = march.step;
+  const int max_steps = march.max_steps;
+  double q0, q1, d[3], enter, leave;
+  cam.ray(col, row, q0, q1);
+  int code = mf_tsdf::ray_setup(P, q0, q1, G, march, d, enter, leave);
   float out = 0.0f;
   int sampled = 0, visited = 0;
   if (code < 0) {
-    const int nbx = ((nx - 2) >> shift) + 1, nby = ((ny - 2) >> shift) + 1;
+    const int nbx = ((G.n[0] - 2) >> shift) + 1, nby = ((G.n[1] - 2) >> shift) + 1;
     bool have = false;
     double prev = 0.0;
     // the jump: `tried` is the block the last attempt started from (a ray meets a block once), (k_pend, pend) a
@@ -110,10 +105,10 @@ __global__ void __launch_bounds__(kTile *kTile) k_tsdf_render(
       if (k == k_pend) {
         g[0] = pend[0], g[1] = pend[1], g[2] = pend[2];
       } else {
-        mf_tsdf::grid_pos(P, d, s, org, pitch, g);
+        mf_tsdf::grid_pos(P, d, s, G, g);
         ++visited;
       }
-      if (!mf_tsdf::cell_of(g, dims, b)) {
+      if (!mf_tsdf::cell_of(g, G, b)) {
         have = false;
         ++sampled;
         continue;
@@ -133,8 +128,8 @@ __global__ void __launch_bounds__(kTile *kTile) k_tsdf_render(
 #pragma unroll
           for (int a = 0; a < 3; ++a) {
             const int top = (I[a] + 1) << shift;
-            const double face = d[a] > 0.0 ? (double)(top < dims[a] - 1 ? top : dims[a] - 1) : (double)(I[a] << shift);
-            const double t = ((org[a] + pitch * face) - P.t[a]) / d[a];
+            const double face = d[a] > 0.0 ? (double)(top < G.n[a] - 1 ? top : G.n[a] - 1) : (double)(I[a] << shift);
+            const double t = ((G.o[a] + G.pitch * face) - P.t[a]) / d[a];
             if ((d[a] < 0.0 || d[a] > 0.0) && t < s_out) s_out = t;
           }
           double kc = floor((s_out - enter) / step);
@@ -148,9 +143,9 @@ __global__ void __launch_bounds__(kTile *kTile) k_tsdf_render(
             }
             if (kj > k + 1 && sj <= leave) {
               double h[3], c[3];
-              mf_tsdf::grid_pos(P, d, sj, org, pitch, h);
+              mf_tsdf::grid_pos(P, d, sj, G, h);
               ++visited;
-              if (mf_tsdf::cell_of(h, dims, c) && ((int)c[0] >> shift) == I0 && ((int)c[1] >> shift) == I1 &&
+              if (mf_tsdf::cell_of(h, G, c) && ((int)c[0] >> shift) == I0 && ((int)c[1] >> shift) == I1 &&
                   ((int)c[2] >> shift) == I2) {
                 k = kj;  // floor(g_a) is monotone in k: every sample up to kj lies in this block
               } else {
@@ -162,7 +157,7 @@ __global__ void __launch_bounds__(kTile *kTile) k_tsdf_render(
         continue;
       }
       ++sampled;
-      const mf_tsdf::Cell cell = mf_tsdf::load_cell(vol, nx, ny, b);
+      const mf_tsdf::Cell cell = mf_tsdf::load_cell(vol, G, b);
       if (!mf_tsdf::all_seen(cell)) { have = false; continue; }
       const double F = mf_tsdf::trilinear(cell, g, b);
       if (F <= 0.0) { code = mf_tsdf::ray_crossing(have, prev, F, enter, step, k, out); break; }
@@ -170,7 +165,7 @@ __global__ void __launch_bounds__(kTile *kTile) k_tsdf_render(
       prev = F;
     }
   }
-  const int64_t p = (int64_t)row * W + col;
+  const int64_t p = cam.pixel(col, row);
   depth_out[p] = out;
   if (code_out) code_out[p] = (uint8_t)code;
   if (stats_out) stats_out[p] = make_int2(sampled, visited);
@@ -178,7 +173,7 @@ __global__ void __launch_bounds__(kTile *kTile) k_tsdf_render(
     // mf_tsdf_label_image on the float32 just stored
     const double dd = (double)out;
     int label = 0;
-    if (dd > 0.0) label = mf_tsdf::label_at(labels, nx, ny, nz, ox, oy, oz, pitch, q0, q1, dd, P, min_count);
+    if (dd > 0.0) label = mf_tsdf::label_at(labels, G, q0, q1, dd, P, min_count);
     label_out[p] = label;
   }
 }
@@ -226,10 +221,9 @@ extern "C" int mf_tsdf_render(const float *volume, int32_t nx, int32_t ny, int32
     return bad("mf_tsdf_render: null volume, T_sensor_to_map, summary or depth_out");
   if ((labels != nullptr) != (label_out != nullptr))
     return bad("mf_tsdf_render: labels and label_out are both null or both non-null");
-  hipLaunchKernelGGL(k_tsdf_render, dim3((unsigned)((W + kTile - 1) / kTile), (unsigned)((H + kTile - 1) / kTile)),
-                     dim3(kTile, kTile), 0, (hipStream_t)stream, volume, (int)nx, (int)ny, (int)nz, origin_x, origin_y,
-                     origin_z, pitch, step, min_depth, max_depth, (int)max_steps, (int)H, (int)W, fx, fy, cx, cy,
-                     T_sensor_to_map, summary, shift, (const int2 *)labels, (int)min_count, depth_out, code_out,
+  hipLaunchKernelGGL(k_tsdf_render, tiles(H, W), dim3(kTile, kTile), 0, (hipStream_t)stream, volume,
+                     grid_of(nx, ny, nz, origin_x, origin_y, origin_z, pitch),
+                     March{step, min_depth, max_depth, max_steps}, camera_of(H, W, fx, fy, cx, cy), T_sensor_to_map, summary, shift, (const int2 *)labels, (int)min_count, depth_out, code_out,
                      label_out, (int2 *)stats_out);
   return mf::check_launch("mf_tsdf_render");
 }
